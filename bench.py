@@ -7,9 +7,13 @@ levels), C=12 feature channels, rgbnet 39->128->128->3, contracted unbounded sce
 fast_color_thres 1e-4.  A "step" = one full frame: ray generation + ray march (density query + alpha + compositing
 scan) + shade (k0 query + rgbnet + weighted sum); grids and camera are resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]          (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]      (N>1: launched by torch.distributed.run)
 
 Prints ONE JSON line on rank 0.  value = Msamples/s = R * S / t_step (all generated samples, before thresholding).
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...); --dump-outputs
+DIR also writes the frame of the last timed step as DIR/<output>.npy.  Everything else -- the per-kernel one-stream region,
+roofline, CPU baseline and parity, scaling proxy, weak scaling, the secondary scenes and training steps, the detail file --
+runs only with --full.
 Multi-GPU is STRONG-scaled: the N ranks render ONE frame -- rank r takes a contiguous band of the frame's 64-ray tiles (--deal rows /
 tiles: block rows or single tiles dealt round-robin) and the rendered tiles [R/N,5] are exchanged with one RCCL all-gather inside the timed step
 (issued asynchronously: frame k's exchange overlaps frame k+1's render; the last one is waited for before the closing
@@ -87,6 +91,11 @@ def parse():
     ap.add_argument("--stepsize", type=float, default=None, help="sampling step in voxels (default 1.31 at G = 200: the 256-sample frame of the metric; "
                     "0.5 = garden_single.py's own sampling, S = 668)")
     ap.add_argument("--cpu-chunks", type=int, default=12, help="8192-ray chunks timed for the CPU baseline (~1 s each)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame the last one computed "
+                    "(rgb_marched, depth, alphainv_last in image order -- also with --shuffle-rays --, float32) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel times and "
+                    "roofline, CPU baseline and parity, scaling proxy / weak scaling / frame assembly check (N > 1), secondary scenes, "
+                    "training steps, detail file")
     return ap.parse_args()
 
 
@@ -465,6 +474,39 @@ def kernel_ms(timing, steps):
     # (pipelined frames carry 4 events per chunk; the kernels of neighbouring chunks overlap then)
     return {"render_march": sum(ev[0].elapsed_time(ev[1]) for ev, _ in timing) / steps,
             "render_shade": sum(ev[-2].elapsed_time(ev[-1]) for ev, _ in timing) / steps}
+
+
+DUMP_BUDGET = 64 * 10 ** 6 - 4096      # bytes of .npy files --dump-outputs may write (64 MB, less room for the headers)
+
+
+def dump_outputs(fb, out_dir):
+    """--dump-outputs: the frame the LAST timed step computed, as a caller of the step receives it -- per-ray rgb_marched [R,3], depth [R],
+    alphainv_last [R] in image order (N > 1: the frame assembled from every rank's tiles; --shuffle-rays: put back from the shuffled
+    order) -- as out_dir/<name>.npy, float32.  A frame larger than DUMP_BUDGET is written as a fixed, seeded sample of its rays (the
+    same rows of every array).  Returns the file names."""
+    import numpy as np
+    keys = ("rgb_marched", "depth", "alphainv_last")
+    if fb.use_dist:
+        f = fb.assembled_frame()
+        outs = {"rgb_marched": f[:, 0:3], "depth": f[:, 3], "alphainv_last": f[:, 4]}
+    else:
+        outs = {k: fb.last_out[k] for k in keys}
+    outs = {k: outs[k].detach().to("cpu", torch.float32).contiguous() for k in keys}
+    perm = getattr(fb, "_perm", None)
+    if perm is not None:        # --shuffle-rays on one rank: the timed steps rendered the shuffled list, row i = pixel perm[i]
+        perm = perm.cpu()
+        outs = {k: torch.empty_like(v).index_copy_(0, perm, v) for k, v in outs.items()}
+    R = outs["depth"].shape[0]
+    per_ray = sum(v.numel() // max(1, R) for v in outs.values()) * 4
+    if R * per_ray > DUMP_BUDGET:
+        g = torch.Generator()
+        g.manual_seed(0)
+        idx = torch.randperm(R, generator=g)[:DUMP_BUDGET // per_ray].sort().values
+        outs = {k: v[idx] for k, v in outs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.numpy())
+    return [k + ".npy" for k in keys]
 
 
 def _profile_path(name, code=None):
@@ -892,6 +934,44 @@ def _standin_renderer(spec):
     return getattr(importlib.import_module(mod), fn)()
 
 
+def headline(args, fb, dt, world, use_dist, n_chunks, standin):
+    """The headline figures of the K timed steps (`dt` seconds): all a plain run reports; --full adds its blocks to this dict."""
+    R, S, G = fb.R, fb.S, args.grid
+    scene_desc = {"s1": "white-noise grids N(%g,%g^2)" % (DENS_MEAN, DENS_STD),
+                  "s1b": "smooth fields with opaque surfaces (make_state_surfaces)"}
+    res = {
+        "metric": "Msamples/sec (Mip-360 garden-shaped 1920x1080x256 frame, FourierGrid render)",
+        "value": R * S / (dt / args.steps) / 1e6, "unit": "Msamples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "rays_per_sec": R / (dt / args.steps),
+        "frames_in_flight": len(fb.pair) if fb.pair is not None else 1,
+        "config": {"workload": "%s %dx%dx%d G%d F%d(P%d) C12 rgbnet 39-128-128-3 f32 stepsize %.3g thres 1e-4 %s"
+                               % (args.scene.upper(), fb.W, fb.H, S, G, args.freq, 1 + 2 * args.freq, fb.stepsize,
+                                  {"s1": "white-noise grids", "s1b": "trained-like fields"}[args.scene]),
+                   "workload_long": "%s: FourierGridModel render, R=%dx%d rays x S=%d samples, G=%d^3, F=%d (P=%d), C=12, "
+                                    "rgbnet 39-128-128-3, stepsize %.3g, thres 1e-4, %s"
+                                    % (args.scene.upper(), fb.W, fb.H, S, G, args.freq, 1 + 2 * args.freq, fb.stepsize, scene_desc[args.scene]),
+                   "rays": R, "samples_per_ray": S, "chunks_per_frame": n_chunks,
+                   "step": "ray generation + march + shade + %s%s" % (
+                       "all-gather of the tiles + frame assembly (un-deal, un-tile)" if use_dist else "un-tiling to image order",
+                       "; %d frames in flight" % len(fb.pair) if fb.pair is not None else ""),
+                   "ray_order": "shuffled (incoherent tiles)" if args.shuffle_rays else (
+                       "%dx%d pixel blocks (one 8x8 block per 64-ray wave), results back in image order" % (args.ray_tile, args.ray_tile)
+                       if fb.order is not None else "image order (64-pixel row segments per wave)"),
+                   "parallelism": ("one frame over %d ranks, %s, 1 all-gather of [R/N,5] tiles per frame (async, overlaps "
+                                   "the next frame)" % (world, "contiguous 64-aligned ray bands" if fb.contiguous
+                                                        else "64-ray tiles (8x8 pixel blocks) dealt round-robin in groups of %d" % fb.deal_group))
+                                   if world > 1 else "1 GPU"},
+    }
+    if standin:
+        res["renderer"] = "stand-in (%s): CI run of the launch / exchange / assembly logic, NOT a measurement" % standin
+    else:
+        res["lib_sha16"] = lib_sha16()
+        res["device_code_sha16"] = device_code_sha16()
+    return res
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -932,8 +1012,6 @@ def main():
             tune(k, int(v))
 
     make = {"s1": make_state, "s1b": make_state_surfaces}
-    scene_desc = {"s1": "white-noise grids N(%g,%g^2)" % (DENS_MEAN, DENS_STD),
-                  "s1b": "smooth fields with opaque surfaces (make_state_surfaces)"}
     G = args.grid
     if standin:
         state = None
@@ -941,7 +1019,7 @@ def main():
     else:
         state = make[args.scene](G, device, seed=0, F=args.freq)  # same model on every rank (replicated read-only grids)
         fb = FrameBench(args, state, device, world, rank, dist)
-    want_cpu = rank == 0 and not args.no_cpu_baseline and not standin
+    want_cpu = args.full and rank == 0 and not args.no_cpu_baseline and not standin
     cpu_state = None
     if want_cpu:
         cpu_state = {k: ([x.cpu() for x in v] if isinstance(v, list) else (v.cpu() if torch.is_tensor(v) else v))
@@ -951,6 +1029,16 @@ def main():
         torch.cuda.empty_cache()
 
     dt, timing = fb.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fb, args.dump_outputs)
+    if not args.full:
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            res = headline(args, fb, dt, world, use_dist, len(timing) // max(1, args.steps), standin)
+            print(json.dumps(compact_line(res, detail=False), separators=(",", ":")))
+        return
     fb.check_exchange()
     # with two frames in flight (the stream pair, default) the march of frame k + 1 runs beside the shade of frame k: the HIP-event duration
     # of a launch then includes its neighbour's work.  The per-kernel durations (`kernels`, `roofline`) come from a SECOND timed region of the
@@ -1010,42 +1098,14 @@ def main():
     res = None
     if rank == 0:
         ms_step = dt / args.steps * 1e3
-        samples = R * S
-        res = {
-            "metric": "Msamples/sec (Mip-360 garden-shaped 1920x1080x256 frame, FourierGrid render)",
-            "value": samples / (dt / args.steps) / 1e6, "unit": "Msamples/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "rays_per_sec": R / (dt / args.steps),
-            "frames_in_flight": len(fb.pair) if fb.pair is not None else 1,
-            "ms_per_step_single_stream": (dt_single / args.steps * 1e3) if dt_single else None,
-            "config": {"workload": "%s %dx%dx%d G%d F%d(P%d) C12 rgbnet 39-128-128-3 f32 stepsize %.3g thres 1e-4 %s"
-                                   % (args.scene.upper(), fb.W, fb.H, S, G, args.freq, 1 + 2 * args.freq, fb.stepsize,
-                                      {"s1": "white-noise grids", "s1b": "trained-like fields"}[args.scene]),
-                       "workload_long": "%s: FourierGridModel render, R=%dx%d rays x S=%d samples, G=%d^3, F=%d (P=%d), C=12, "
-                                        "rgbnet 39-128-128-3, stepsize %.3g, thres 1e-4, %s"
-                                        % (args.scene.upper(), fb.W, fb.H, S, G, args.freq, 1 + 2 * args.freq, fb.stepsize, scene_desc[args.scene]),
-                       "rays": R, "samples_per_ray": S, "survivors_M": M, "survivor_frac": M / float(R * S),
-                       "terminated_ray_frac": term_frac, "chunks_per_frame": n_chunks,
-                       "step": "ray generation + march + shade + %s%s" % (
-                           "all-gather of the tiles + frame assembly (un-deal, un-tile)" if use_dist else "un-tiling to image order",
-                           "; %d frames in flight" % len(fb.pair) if fb.pair is not None else ""),
-                       "ray_order": "shuffled (incoherent tiles)" if args.shuffle_rays else (
-                           "%dx%d pixel blocks (one 8x8 block per 64-ray wave), results back in image order" % (args.ray_tile, args.ray_tile)
-                           if fb.order is not None else "image order (64-pixel row segments per wave)"),
-                       "parallelism": ("one frame over %d ranks, %s, 1 all-gather of [R/N,5] tiles per frame (async, overlaps "
-                                       "the next frame)" % (world, "contiguous 64-aligned ray bands" if fb.contiguous
-                                                            else "64-ray tiles (8x8 pixel blocks) dealt round-robin in groups of %d" % fb.deal_group))
-                                       if world > 1 else "1 GPU"},
-            "kernels": {k: {"ms": v} for k, v in kern.items()},
-        }
+        res = headline(args, fb, dt, world, use_dist, n_chunks, standin)
+        res["ms_per_step_single_stream"] = (dt_single / args.steps * 1e3) if dt_single else None
+        res["config"].update({"survivors_M": M, "survivor_frac": M / float(R * S), "terminated_ray_frac": term_frac})
+        res["kernels"] = {k: {"ms": v} for k, v in kern.items()}
         if standin:
-            res["renderer"] = "stand-in (%s): CI run of the launch / exchange / assembly logic, NOT a measurement" % standin
             res["roofline"] = None
         else:
-            res["lib_sha16"] = lib_sha16()
             res["frame_sha16"] = frame_sha
-            res["device_code_sha16"] = device_code_sha16()
             if M_rank is not None:
                 # rank 0's own kernels: its share of the frame's rays and survivors (the whole frame at N = 1)
                 shade_passes = (M_rank + 31) // 32 + rays_this_rank // 64 // 2      # ~ sum over tiles of ceil(count / 32)
@@ -1168,10 +1228,10 @@ def write_detail(res, path=None):
     return {"path": os.path.relpath(path, ROOT), "sha16": hashlib.sha256(blob).hexdigest()[:16], "bytes": len(blob)}
 
 
-def compact_line(res, detail_path=None):
+def compact_line(res, detail_path=None, detail=True):
     """The ONE line the driver parses: the contract's keys, `roofline` / `roofline_hbm` / `cpu_baseline` as numbers only, one
-    number (ms per step) per secondary, and where the rest went (`detail`: bench_detail.json + its sha16).  Always < LINE_BUDGET
-    bytes (tests/test_host_logic.py::test_bench_line_fits_the_driver)."""
+    number (ms per step) per secondary, and where the rest went (`detail`: bench_detail.json + its sha16; detail=False: a plain
+    run's line, no file).  Always < LINE_BUDGET bytes (tests/test_host_logic.py::test_bench_line_fits_the_driver)."""
     line = {k: _num(res.get(k), 6) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                              "scaling", "vs_baseline", "dtype", "data", "rays_per_sec", "frames_in_flight",
                                              "ms_per_step_single_stream") if k in res}
@@ -1180,7 +1240,8 @@ def compact_line(res, detail_path=None):
     line["config"].update(_pick(cfg, ("rays", "samples_per_ray", "survivors_M", "survivor_frac", "chunks_per_frame")))
     line["config"]["parallelism"] = str(cfg.get("parallelism", ""))[:60]
     line["config"]["step"] = str(cfg.get("step", ""))[:100]
-    line["kernels"] = {k: _num(v.get("ms")) for k, v in (res.get("kernels") or {}).items()}
+    if "kernels" in res:
+        line["kernels"] = {k: _num(v.get("ms")) for k, v in (res.get("kernels") or {}).items()}
     for k in ("renderer", "lib_sha16", "device_code_sha16", "frame_sha16", "assembled_frame_equals_single_rank_frame"):
         if k in res:
             line[k] = res[k]
@@ -1191,7 +1252,7 @@ def compact_line(res, detail_path=None):
         pk = rf.get("per_kernel") or {}
         line["roofline"]["per_kernel"] = {k: _pick(v, ("ms", "l1_frac", "hbm_frac", "mfma_frac", "ta_busy_measured", "mfma_pipe_busy", "valu_issue_busy",
                                                        "rocprofv3_avg_ms"), 3) for k, v in pk.items()}
-    else:
+    elif "roofline" in res:
         line["roofline"] = None
     rh = res.get("roofline_hbm")
     if isinstance(rh, dict):
@@ -1258,7 +1319,8 @@ def compact_line(res, detail_path=None):
     if isinstance(px, dict) and isinstance(px.get("N=8"), dict):
         b = px["N=8"].get("contiguous_bands") or {}
         line["scaling_proxy_N8"] = _pick(b, ("slowest_share_ms", "predicted_speedup", "frame_pair_slowest_share_ms", "frame_pair_predicted_speedup"))
-    line["detail"] = write_detail(res, detail_path)
+    if detail:
+        line["detail"] = write_detail(res, detail_path)
     n = len(json.dumps(line, separators=(",", ":")))
     if n >= LINE_BUDGET:            # never print an unparseable line: drop the optional blocks, largest first
         for k in ("secondary_ms", "scaling_proxy_N8", "weak_scaling", "roofline_hbm"):

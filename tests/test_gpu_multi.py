@@ -170,16 +170,19 @@ def test_sharded_masked_adam_over_rccl_equals_the_single_process_optimizer(world
 
 
 @need2
-def test_bench_py_gpus_2_over_rccl():
-    """the driver's N = 2 command line (bench.py launches itself through torch.distributed.run on 127.0.0.1)"""
+def test_bench_py_gpus_2_over_rccl(tmp_path):
+    """the driver's N = 2 command line (bench.py launches itself through torch.distributed.run on 127.0.0.1), with --full: the
+    frame-assembly check and the per-rank shares (the latter in the detail file the line names)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["UGRID_BENCH_DETAIL"] = str(tmp_path / "bench_detail.json")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-secondary"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-secondary", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     res = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
-    print(json.dumps({k: res[k] for k in ("value", "ms_per_step", "n_gpus", "per_rank", "assembled_frame_equals_single_rank_frame")}))
+    full = json.load(open(env["UGRID_BENCH_DETAIL"]))
+    print(json.dumps(dict({k: res[k] for k in ("value", "ms_per_step", "n_gpus", "assembled_frame_equals_single_rank_frame")}, per_rank=full["per_rank"])))
     assert res["n_gpus"] == 2 and res["assembled_frame_equals_single_rank_frame"] is True
-    assert sum(r["rays"] for r in res["per_rank"]) == 1920 * 1080
+    assert sum(r["rays"] for r in full["per_rank"]) == 1920 * 1080
 
 
 @pytest.mark.parametrize("world", WORLDS)

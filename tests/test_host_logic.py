@@ -780,7 +780,7 @@ def test_bench_launches_itself_for_n_gt_1(tmp_path):
     detail = str(tmp_path / "bench_detail.json")
     env["UGRID_BENCH_DETAIL"] = detail
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "40",
-                        "--width", "104"], env=env, capture_output=True, text=True, timeout=300)
+                        "--width", "104", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -799,6 +799,80 @@ def test_bench_launches_itself_for_n_gt_1(tmp_path):
     env2 = dict(env, WORLD_SIZE="3", RANK="0")
     p2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env2, capture_output=True, text=True, timeout=120)
     assert p2.returncode != 0 and "WORLD_SIZE=3" in (p2.stderr + p2.stdout)
+
+
+@pytest.mark.parametrize("gpus,extra", [(1, []), (2, []), (1, ["--shuffle-rays"])])
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_frame(tmp_path, gpus, extra):
+    """A plain run (no --full) times exactly --steps steps after --warmup ones, prints the headline keys and nothing it did not measure,
+    writes no detail file, and --dump-outputs DIR holds the frame of the LAST timed step in image order (N = 2: the frame assembled from
+    both ranks' tiles; --shuffle-rays: put back from the shuffled order) -- the same arrays run after run.  The CPU stand-in's depth
+    carries the number of renderer calls so far: the dumped frame must be call warmup + steps on every rank."""
+    import argparse
+    import json
+    import subprocess
+    import bench_standin
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["UGRID_BENCH_STANDIN"] = "bench_standin:CountingRenderer"
+    env["OMP_NUM_THREADS"] = "1"
+    env["UGRID_BENCH_DETAIL"] = str(tmp_path / "bench_detail.json")
+    H, W = 40, 104
+    dumps = []
+    for rep, (steps, warmup) in enumerate(((3, 1), (3, 1), (2, 3))):
+        d = tmp_path / ("out%d" % rep)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup),
+                            "--height", str(H), "--width", str(W), "--dump-outputs", str(d)] + extra,
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        res = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+            assert k in res, k
+        assert res["steps"] == steps and res["warmup"] == warmup and res["n_gpus"] == gpus and res["ms_per_step"] > 0
+        assert res["value"] == pytest.approx(H * W * res["config"]["samples_per_ray"] / (res["ms_per_step"] * 1e-3) / 1e6, rel=1e-4)
+        for k in ("kernels", "roofline", "cpu_baseline", "weak_scaling", "detail", "secondary_ms", "scaling_proxy_N8"):
+            assert k not in res, k
+        dumps.append((warmup + steps, {n: np.load(str(d / (n + ".npy"))) for n in ("rgb_marched", "depth", "alphainv_last")}))
+    assert not (tmp_path / "bench_detail.json").exists()
+    import bench
+    args = argparse.Namespace(height=H, width=W, grid=200, contiguous=False, pipeline=0, mlp_mode=None, ray_tile=0)
+    fb = bench.FrameBench(args, None, torch.device("cpu"), 1, 0, None, renderer=_FakeRenderer())
+    rays = fb.rays()                    # image order
+    for calls, got in dumps:
+        want = bench_standin.CountingRenderer()
+        want.calls = calls - 1
+        want = want(*rays)              # = call number `calls`
+        for n in ("rgb_marched", "depth", "alphainv_last"):
+            assert got[n].dtype == np.float32
+            np.testing.assert_array_equal(got[n], want[n].numpy())
+    for n in dumps[0][1]:
+        np.testing.assert_array_equal(dumps[0][1][n], dumps[1][1][n])
+
+
+def test_bench_dump_samples_a_frame_beyond_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs of a frame larger than DUMP_BUDGET: within the budget, the same fixed, seeded rows of every output -- each
+    sampled row is the stand-in's output for the ray of that pixel, in every array."""
+    import argparse
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    H, W = 40, 104
+    args = argparse.Namespace(height=H, width=W, grid=200, contiguous=False, pipeline=0, mlp_mode=None, ray_tile=8)
+    fb = bench.FrameBench(args, None, torch.device("cpu"), 1, 0, None, renderer=_FakeRenderer())
+    fb.timed(1, 0)
+    img = bench.FrameBench(argparse.Namespace(**dict(vars(args), ray_tile=0)), None, torch.device("cpu"), 1, 0, None, renderer=_FakeRenderer())
+    want = _FakeRenderer()(*img.rays())                    # image order
+    g = torch.Generator()
+    g.manual_seed(0)
+    rows = torch.randperm(H * W, generator=g)[:4000 // 20].sort().values       # 20 bytes per ray: rgb 3 + depth + alphainv_last, fp32
+    blobs = []
+    for rep in range(2):
+        bench.dump_outputs(fb, str(tmp_path / str(rep)))
+        got = {n: np.load(str(tmp_path / str(rep) / (n + ".npy"))) for n in ("rgb_marched", "depth", "alphainv_last")}
+        assert sum(v.nbytes for v in got.values()) <= 4000
+        for n, v in got.items():
+            np.testing.assert_array_equal(v, want[n][rows].numpy())
+        blobs.append(open(str(tmp_path / str(rep) / "rgb_marched.npy"), "rb").read())
+    assert blobs[0] == blobs[1]
 
 
 def test_bench_line_fits_the_driver(tmp_path):
@@ -1080,22 +1154,31 @@ def test_maybe_scale_grids_serves_both_model_families():
     assert built == [0] * 9
 
 
-def test_install_model_classes_rebinds_the_reference_classes():
+def test_install_model_classes_rebinds_the_reference_classes(monkeypatch):
     """compat.install_model_classes: the reference's dvgo / dcvgo / FourierGrid_model modules then hand out this package's training
-    models (same constructor arguments: built here with the reference's own keyword names), and the originals come back"""
-    import sys
-    import pytest
-    from oracle import install_stubs
-    if not install_stubs.reference_available():
-        pytest.skip("reference tree not present")
+    models (same constructor arguments: built here with the reference's own keyword names), and the originals come back.  The
+    function only rebinds attributes of the modules `FourierGrid.<name>` imports to, so those modules are stand-ins registered
+    under the reference's names (each with its class, and run_train with its by-name import): nothing outside the repository."""
+    import types
     from unboundednerfpytorch_amd import compat, fourier_model, voxgo_model
-    dvgo = install_stubs.import_reference("dvgo")
-    dcvgo = install_stubs.import_reference("dcvgo")
-    fgm = install_stubs.import_reference("FourierGrid_model")
+    pkg = types.ModuleType("FourierGrid")
+    pkg.__path__ = []
+    monkeypatch.setitem(sys.modules, "FourierGrid", pkg)
+    mods = {}
+    for name, cls in (("dvgo", "DirectVoxGO"), ("dcvgo", "DirectContractedVoxGO"), ("FourierGrid_model", "FourierGridModel")):
+        m = types.ModuleType("FourierGrid." + name)
+        setattr(m, cls, type(cls, (torch.nn.Module,), {}))
+        setattr(pkg, name, m)
+        monkeypatch.setitem(sys.modules, m.__name__, m)
+        mods[name] = m
+    dvgo, dcvgo, fgm = mods["dvgo"], mods["dcvgo"], mods["FourierGrid_model"]
+    run_train = types.ModuleType("FourierGrid.run_train")
+    run_train.FourierGridModel = fgm.FourierGridModel             # run_train.py:10 binds the class by name at import
+    monkeypatch.setitem(sys.modules, run_train.__name__, run_train)
     orig = compat.install_model_classes()
     try:
         assert dvgo.DirectVoxGO is voxgo_model.DirectVoxGO and dcvgo.DirectContractedVoxGO is voxgo_model.DirectContractedVoxGO
-        assert fgm.FourierGridModel is fourier_model.FourierGridModel
+        assert fgm.FourierGridModel is fourier_model.FourierGridModel and run_train.FourierGridModel is fourier_model.FourierGridModel
         # create_new_model's call shapes (run_train.py:32-50), incl. the extra keys its **model_kwargs carry
         extra = dict(num_voxels_base_density=8 ** 3, num_voxels_base_rgb=8 ** 3, num_voxels_viewdir=-1, density_type='DenseGrid',
                      k0_type='DenseGrid', density_config={}, k0_config={}, mpi_depth=128, nearest=False, pre_act_density=False,

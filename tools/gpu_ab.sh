@@ -11,7 +11,7 @@ STEPS=${AB_STEPS:-12}
 for lib in "$@"; do
   for rep in $(seq 1 ${AB_REPS:-1}); do
     LINE=$OUT/line_${AB_NAME:-ab}_$(basename $lib)_$rep.json
-    UGRID_LIB=$PWD/$lib timeout 300 python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline --no-secondary $BENCH_FLAGS 2>$OUT/err_$(basename $lib).log | tail -1 > $LINE
+    UGRID_LIB=$PWD/$lib timeout 300 python bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline --no-secondary $BENCH_FLAGS 2>$OUT/err_$(basename $lib).log | tail -1 > $LINE
     python - "$lib" $LINE <<'PY' | tee -a $OUT/ab.txt
 import json, sys
 try:
