@@ -380,6 +380,25 @@ int ugrid_render_march_dvgo(const ugrid_render_params *h_params, const ugrid_dvg
                             const float *rays_d, const float *density_bricks, float *alphainv_last, float *depth,
                             void *ws, ugrid_stream_t stream);
 
+/* Fused march of the reference's forward-facing DirectMPIGO.forward (dmpigo.py:224-338; single-level grids,
+ * h_params->freq_num = 0, h_params->xyz_min / xyz_max = the NDC scene box, h_params->act_shift = 0): every ray takes the
+ * same n_steps samples p = o + d * (step / (n_steps - 1)) (sample_ndc_pts_on_rays, render_utils_kernel.cu:245-270; NDC
+ * rays, near = 0, far = 1), mask_outbbox and the mask cache before the lookup, density = the density grid at p + the
+ * per-plane shift act_shift [mpi_depth] (a DenseGrid of shape [1,1,1,1,mpi_depth], dmpigo.py:47-57: interpolated along z
+ * only) -- two interpolations added in fp32 --, then Raw2Alpha with shift 0, thresholds, compositing as above;
+ * depth = sum w * (step + 0.5) / n_steps (dmpigo.py:319-338).  h_params->n_samples >= n_steps sizes the survivor list
+ * in ws, which feeds ugrid_render_shade (freq_num = 0).  mpi_depth <= 256. */
+typedef struct ugrid_mpi_params {
+  const uint8_t *mask;              /* DEVICE bool [mask_x][mask_y][mask_z] */
+  int32_t mask_x, mask_y, mask_z;
+  float xyz2ijk_scale[3], xyz2ijk_shift[3];
+  int32_t mpi_depth;                /* planes of act_shift (= grid_z) */
+  int32_t n_steps;                  /* int((mpi_depth - 1) / stepsize) + 1 */
+} ugrid_mpi_params;
+int ugrid_render_march_mpi(const ugrid_render_params *h_params, const ugrid_mpi_params *h_mpi, const float *rays_o,
+                           const float *rays_d, const float *density_bricks, const float *act_shift, float *alphainv_last,
+                           float *depth, void *ws, ugrid_stream_t stream);
+
 /* Fused shade: survivors -> P-level k0 bricks -> [k0, viewdir emb] -> rgbnet (MFMA, h_params->mlp_mode) -> sigmoid
  * -> weighted per-ray sum in sample order; writes rgb_marched [R,3].  mlp_packed: ugrid_pack_mlp(). */
 int ugrid_render_shade(const ugrid_render_params *h_params, const float *viewdirs,
@@ -415,6 +434,13 @@ int ugrid_mlp_fp16x2_scales(const float *h_w0, const float *h_b0, const float *h
 int ugrid_rays_of_a_view(int32_t H, int32_t W, const float *h_K9, const float *c2w, int inverse_y, int flip_x, int flip_y,
                          int mode_center, const int64_t *pixel_index, int64_t n, float *rays_o, float *rays_d,
                          float *viewdirs, ugrid_stream_t stream);
+/* The same with ndc=True (dvgo.py:534-559, forward-facing scenes): viewdirs = the normalised WORLD direction, rays_o /
+ * rays_d = ndc_rays(H, W, K[0][0], near, world rays) -- the reference passes near = 1 --, with the operation order of its
+ * torch chain (Python-number constants rounded to fp32 where they meet the tensors; `number / tensor` as
+ * reciprocal(tensor) * number). */
+int ugrid_rays_of_a_view_ndc(int32_t H, int32_t W, const float *h_K9, const float *c2w, int inverse_y, int flip_x, int flip_y,
+                             int mode_center, const int64_t *pixel_index, int64_t n, float near, float *rays_o,
+                             float *rays_d, float *viewdirs, ugrid_stream_t stream);
 
 /* ------------------------------------------------------------------ fused training forward, stage 1 (new)
  * Replaces the head of FourierGridModel.forward in training mode (FourierGrid_model.py:554-598): sample_ray, the

@@ -57,6 +57,13 @@ class DvgoParams(_c.Structure):
                 ("far_clip", _c.c_float), ("stepdist", _c.c_float)]
 
 
+class MpiParams(_c.Structure):
+    """Mirror of `ugrid_mpi_params` (include/ugrid_hip.h)."""
+    _fields_ = [("mask", _c.c_void_p), ("mask_x", _c.c_int32), ("mask_y", _c.c_int32), ("mask_z", _c.c_int32),
+                ("xyz2ijk_scale", _c.c_float * 3), ("xyz2ijk_shift", _c.c_float * 3), ("mpi_depth", _c.c_int32),
+                ("n_steps", _c.c_int32)]
+
+
 class AdamItem(_c.Structure):
     """ugrid_adam_item (include/ugrid_hip.h)"""
     _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p),
@@ -120,6 +127,7 @@ _SIGNATURES = {
     "ugrid_grid_query": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _L, _P, _P]),
     "ugrid_grid_query_backward": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _L, _P, _P]),
     "ugrid_rays_of_a_view": (_I, [_c.c_int32, _c.c_int32, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
+    "ugrid_rays_of_a_view_ndc": (_I, [_c.c_int32, _c.c_int32, _P, _P, _I, _I, _I, _I, _P, _L, _F, _P, _P, _P, _P]),
     "ugrid_train_march": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _L, _P, _c.c_int32, _P, _P, _P, _P, _c.c_double, _I, _F, _F, _F,
                                 _P, _P, _P, _P, _P]),
     "ugrid_train_compact": (_I, [_L, _c.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -160,6 +168,7 @@ _SIGNATURES = {
     "ugrid_render_march": (_I, [_c.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ugrid_render_march_dcvgo": (_I, [_c.POINTER(RenderParams), _c.POINTER(DcvgoParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ugrid_render_march_dvgo": (_I, [_c.POINTER(RenderParams), _c.POINTER(DvgoParams), _P, _P, _P, _P, _P, _P, _P]),
+    "ugrid_render_march_mpi": (_I, [_c.POINTER(RenderParams), _c.POINTER(MpiParams), _P, _P, _P, _P, _P, _P, _P, _P]),
     "ugrid_render_shade": (_I, [_c.POINTER(RenderParams), _P, _P, _P, _P, _P, _P]),
     "ugrid_mlp_packed_bytes": (_L, [_c.c_int32, _c.c_int32]),
     "ugrid_pack_mlp": (_I, [_P, _P, _P, _P, _P, _P, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_float, _P,

@@ -950,6 +950,23 @@ k_march_dvgo(ug_march_args a, ug_dv_args dv, const float *__restrict__ rays_o, c
   if (ug_lane() == 0) ws.count[tile] = n;
 }
 
+// forward-facing DirectMPIGO march (ug_march_tile_mpi): NDC rays, n samples each; act_shift [D <= 256] staged in LDS
+__global__ void __launch_bounds__(256, 6)
+k_march_mpi(ug_march_args a, ug_mpi_args mp, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+            const float *__restrict__ bricks, const float *__restrict__ act_shift, float *__restrict__ alphainv_last,
+            float *__restrict__ depth, ug_ws_view ws, int64_t nblocks) {
+  __shared__ float shift[256];
+  if ((int)threadIdx.x < mp.D) shift[threadIdx.x] = act_shift[threadIdx.x];
+  __syncthreads();
+  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
+  if (blk >= nblocks) return;
+  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
+  if (tile >= ws.n_tiles) return;
+  const int n = ug_march_tile_mpi(a, mp, rays_o, rays_d, bricks, shift, alphainv_last, depth, tile, ws.ent + tile * ws.cap,
+                                  ws.slot + tile * ws.cap);
+  if (ug_lane() == 0) ws.count[tile] = n;
+}
+
 // ----------------------------------------------------------------------------------------------
 // C ABI
 // ----------------------------------------------------------------------------------------------
@@ -1159,3 +1176,28 @@ extern "C" int ugrid_render_march_dvgo(const ugrid_render_params *p, const ugrid
 }
 
 
+
+extern "C" int ugrid_render_march_mpi(const ugrid_render_params *p, const ugrid_mpi_params *q, const float *rays_o,
+                                      const float *rays_d, const float *density_bricks, const float *act_shift, float *alphainv_last,
+                                      float *depth, void *ws_mem, ugrid_stream_t s) {
+  if (p->n_rays <= 0) return 0;
+  if (p->freq_num != 0 || !q || !q->mask || q->mask_x < 1 || q->mask_y < 1 || q->mask_z < 1 || !act_shift)
+    return (int)hipErrorInvalidValue;
+  // the LDS table holds 256 planes; a lane's samples fill at most n_samples entries of its tile's survivor list
+  if (q->mpi_depth < 2 || q->mpi_depth > 256 || q->n_steps < 2 || q->n_steps > p->n_samples) return (int)hipErrorInvalidValue;
+  ug_march_args a;
+  const int rc = ug_fill_march_args(p, a);
+  if (rc) return rc;
+  ug_mpi_args mp;
+  mp.mask = q->mask; mp.mi = q->mask_x; mp.mj = q->mask_y; mp.mk = q->mask_z;
+  mp.sx = q->xyz2ijk_scale[0]; mp.sy = q->xyz2ijk_scale[1]; mp.sz = q->xyz2ijk_scale[2];
+  mp.hx = q->xyz2ijk_shift[0]; mp.hy = q->xyz2ijk_shift[1]; mp.hz = q->xyz2ijk_shift[2];
+  mp.D = q->mpi_depth; mp.n = q->n_steps;
+  ug_ws_view ws = ug_ws_make(ws_mem, p->n_rays, p->n_samples);
+  const int64_t nblocks = (ws.n_tiles + 3) / 4;
+  const int64_t grid = ((nblocks + 7) / 8) * 8;  // room for the XCD remap
+  hipLaunchKernelGGL(k_march_mpi, dim3((unsigned)grid), dim3(256), 0, ST(s), a, mp, rays_o, rays_d, density_bricks, act_shift,
+                     alphainv_last, depth, ws, nblocks);
+  UG_LAUNCH_CHECK();
+  return 0;
+}

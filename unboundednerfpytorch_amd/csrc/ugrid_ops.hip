@@ -765,11 +765,8 @@ k_tv_adam_vec4(const float *__restrict__ param, float *__restrict__ param_out, c
 // ----------------------------------------------------------------------------------------------
 struct ug_cam { float fx, fy, cx, cy; int W, H, inverse_y, flip_x, flip_y, center; };
 
-__global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
-                                 float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int64_t p = pix ? pix[t] : t;
+// world-space direction of flat pixel p (get_rays, dvgo.py:493-521)
+__device__ __forceinline__ void ug_view_ray_dir(const ug_cam &c, const float *__restrict__ c2w, int64_t p, float (&r)[3]) {
   int j = (int)(p / c.W), i = (int)(p - (int64_t)j * c.W);
   if (c.flip_x) i = c.W - 1 - i;
   if (c.flip_y) j = c.H - 1 - j;
@@ -778,12 +775,19 @@ __global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const 
   float dx, dy, dz;
   if (c.inverse_y) { dx = (ii - c.cx) / c.fx; dy = (jj - c.cy) / c.fy; dz = 1.0f; }
   else { dx = (ii - c.cx) / c.fx; dy = -(jj - c.cy) / c.fy; dz = -1.0f; }
-  float r[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float p0 = dx * c2w[4 * a], p1 = dy * c2w[4 * a + 1], p2 = dz * c2w[4 * a + 2];
     r[a] = (p0 + p1) + p2;
   }
+}
+
+__global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
+                                 float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  float r[3];
+  ug_view_ray_dir(c, c2w, pix ? pix[t] : t, r);
   const float nrm = sqrtf(fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0])));
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -791,6 +795,32 @@ __global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const 
     rays_d[3 * t + a] = r[a];
     viewdirs[3 * t + a] = r[a] / nrm;
   }
+}
+
+// get_rays_of_a_view(ndc=True) (dvgo.py:534-559): viewdirs from the WORLD direction, then ndc_rays(H, W, K[0][0], near, o, d)
+// in the order of its torch chain: t = -(o_z + near) / d_z; o' = o + t * d; 2 * near / o'_z as reciprocal(o'_z) * (2 near)
+// (Tensor.__rtruediv__); the Python constants -1 / (W / (2 focal)) etc. are formed in double on the host and rounded to fp32.
+struct ug_ndc { float near, kx, ky, two_near, mtwo_near; };
+
+__global__ void k_rays_of_a_view_ndc(ug_cam c, ug_ndc q, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
+                                     float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  float r[3];
+  ug_view_ray_dir(c, c2w, pix ? pix[t] : t, r);
+  const float nrm = sqrtf(fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0])));
+#pragma unroll
+  for (int a = 0; a < 3; ++a) viewdirs[3 * t + a] = r[a] / nrm;
+  const float wx = c2w[3], wy = c2w[7], wz = c2w[11];
+  const float tt = -(wz + q.near) / r[2];
+  const float ox = wx + tt * r[0], oy = wy + tt * r[1], oz = wz + tt * r[2];
+  const float rz = 1.0f / oz;
+  rays_o[3 * t] = q.kx * ox / oz;
+  rays_o[3 * t + 1] = q.ky * oy / oz;
+  rays_o[3 * t + 2] = 1.0f + rz * q.two_near;
+  rays_d[3 * t] = q.kx * (r[0] / r[2] - ox / oz);
+  rays_d[3 * t + 1] = q.ky * (r[1] / r[2] - oy / oz);
+  rays_d[3 * t + 2] = rz * q.mtwo_near;
 }
 
 
@@ -1247,6 +1277,27 @@ extern "C" int ugrid_rays_of_a_view(int32_t H, int32_t W, const float *h_K9, con
   c.W = W; c.H = H; c.inverse_y = inverse_y; c.flip_x = flip_x; c.flip_y = flip_y; c.center = mode_center;
   hipLaunchKernelGGL(k_rays_of_a_view, dim3(ug_blocks(n, 256)), dim3(256), 0, ST(s), c, c2w, pixel_index, n, rays_o, rays_d,
                      viewdirs);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_rays_of_a_view_ndc(int32_t H, int32_t W, const float *h_K9, const float *c2w, int inverse_y, int flip_x,
+                                        int flip_y, int mode_center, const int64_t *pixel_index, int64_t n, float near,
+                                        float *rays_o, float *rays_d, float *viewdirs, ugrid_stream_t s) {
+  if (n <= 0) return 0;
+  if (H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
+  ug_cam c;
+  c.fx = h_K9[0]; c.fy = h_K9[4]; c.cx = h_K9[2]; c.cy = h_K9[5];
+  c.W = W; c.H = H; c.inverse_y = inverse_y; c.flip_x = flip_x; c.flip_y = flip_y; c.center = mode_center;
+  ug_ndc q;
+  const double focal = (double)h_K9[0], nr = (double)near;
+  q.near = near;
+  q.kx = (float)(-1. / ((double)W / (2. * focal)));
+  q.ky = (float)(-1. / ((double)H / (2. * focal)));
+  q.two_near = (float)(2. * nr);
+  q.mtwo_near = (float)(-2. * nr);
+  hipLaunchKernelGGL(k_rays_of_a_view_ndc, dim3(ug_blocks(n, 256)), dim3(256), 0, ST(s), c, q, c2w, pixel_index, n, rays_o,
+                     rays_d, viewdirs);
   UG_LAUNCH_CHECK();
   return 0;
 }

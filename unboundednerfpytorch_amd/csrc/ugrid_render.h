@@ -426,6 +426,96 @@ __device__ __forceinline__ int ug_march_tile_dvgo(const ug_march_args &a, const 
 }
 
 // ----------------------------------------------------------------------------------------------
+// Forward-facing DirectMPIGO march (dmpigo.py:224-338): NDC rays, every ray takes the same n samples
+// p = o + d * (step / (n-1)) (sample_ndc_pts_on_rays, render_utils_kernel.cu:245-270) -- a wave-uniform loop bound, no
+// clipping, no count kernel.  mask_outbbox and the mask cache as in the DirectVoxGO tile, then density = the density grid
+// + act_shift, the per-plane shift grid [1,1,1,1,D] (dmpigo.py:47-57): grid_sample with align_corners = True maps its
+// one-voxel x / y axes to index 0 with weight 1, so it is a lerp along z of the D-entry table `shift` (LDS), formed like
+// grid_sample forms it (v0 * w0 + v1 * w1; a corner beyond the last plane is not added).  The two interpolations are
+// added in fp32 like the reference's `self.density(p) + self.act_shift(p)`; Raw2Alpha then gets shift 0.
+// depth = sum w * (step + 0.5) / n (dmpigo.py:319: int64 + 0.5 promotes to fp32).
+// ----------------------------------------------------------------------------------------------
+struct ug_mpi_args {
+  const uint8_t *mask;
+  int32_t mi, mj, mk;
+  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+  int32_t D, n;                     // mpi_depth, samples per ray
+};
+
+__device__ __forceinline__ int ug_march_tile_mpi(const ug_march_args &a, const ug_mpi_args &mp, const float *__restrict__ rays_o,
+                                                 const float *__restrict__ rays_d, const float *__restrict__ bricks,
+                                                 const float *__restrict__ shift, float *__restrict__ alphainv_last,
+                                                 float *__restrict__ depth, int64_t tile, float4 *__restrict__ ent,
+                                                 uint8_t *__restrict__ slot) {
+  const int lane = ug_lane();
+  const int64_t ray = tile * UG_WAVE + lane;
+  const bool valid = ray < a.n_rays;
+  float ox = 0.f, oy = 0.f, oz = 0.f, rx = 0.f, ry = 0.f, rz = 0.f;
+  if (valid) {
+    ox = rays_o[3 * ray]; oy = rays_o[3 * ray + 1]; oz = rays_o[3 * ray + 2];
+    rx = rays_d[3 * ray]; ry = rays_d[3 * ray + 1]; rz = rays_d[3 * ray + 2];
+  }
+  const char *__restrict__ bkb = (const char *)bricks;
+  const float dm1 = (float)(mp.D - 1), nm1 = (float)(mp.n - 1), nf = (float)mp.n;
+  float T = 1.f, dsum = 0.f;
+  bool done = !valid;
+  int nsurv = 0;  // wave-uniform
+  for (int j = 0; j < mp.n; ++j) {
+    if (__ballot(!done) == 0ull) break;
+    bool surv = false;
+    float w = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+    if (!done) {
+      const float dist = (float)j / nm1;
+      px = ox + rx * dist; py = oy + ry * dist; pz = oz + rz * dist;
+      bool keep = !((a.lox > px) | (a.loy > py) | (a.loz > pz) | (a.hix < px) | (a.hiy < py) | (a.hiz < pz));   // mask_outbbox
+      if (keep) {       // mask cache (k_maskcache semantics)
+        float fi = roundf(px * mp.sx + mp.hx), fj = roundf(py * mp.sy + mp.hy), fk = roundf(pz * mp.sz + mp.hz);
+        fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
+        keep = false;
+        if (fi >= 0.f && fi < (float)mp.mi && fj >= 0.f && fj < (float)mp.mj && fk >= 0.f && fk < (float)mp.mk)
+          keep = mp.mask[((int64_t)fi * mp.mj + (int64_t)fj) * mp.mk + (int64_t)fk] != 0;
+      }
+      if (keep) {
+        const float ux = ug_div_r(px - a.lox, a.ex, a.irx) * 2.f - 1.f;
+        const float uy = ug_div_r(py - a.loy, a.ey, a.iry) * 2.f - 1.f;
+        const float uz = ug_div_r(pz - a.loz, a.ez, a.irz) * 2.f - 1.f;
+        const float dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
+        // act_shift: uz in [-1, 1] for a point inside the box, so iz in [0, D-1]
+        const float iz = ((uz + 1.f) / 2.f) * dm1;
+        const float f0 = floorf(iz);
+        const int i0 = min(max((int)f0, 0), mp.D - 1);
+        float sh = shift[i0] * ((f0 + 1.f) - iz);
+        if (i0 + 1 < mp.D) sh = sh + shift[i0 + 1] * (iz - f0);
+        const float alpha = ug_alpha(dens + sh, a.interval);
+        if (alpha > a.thres) {
+          w = T * alpha;
+          T = (float)((double)T * (1. - (double)alpha));
+          if (w > a.thres) {
+            surv = true;
+            dsum += w * (((float)j + 0.5f) / nf);
+          }
+          if ((double)T < 1e-3) done = true;
+        }
+      }
+    }
+    const unsigned long long m = __ballot(surv);
+    if (m != 0ull) {
+      if (surv) {
+        const int idx = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        ent[idx] = make_float4(px, py, pz, w);
+        slot[idx] = (uint8_t)lane;
+      }
+      nsurv += __popcll(m);
+    }
+  }
+  if (valid) {
+    alphainv_last[ray] = T;
+    depth[ray] = dsum;
+  }
+  return nsurv;
+}
+
+// ----------------------------------------------------------------------------------------------
 // rgbnet packing for the transposed MFMA chain
 // packed (floats): A1 [KL][64][4] | A2 [64][64][4] | bias1 [2][64] | bias2 [2][64] | W3 [2][64][4] | b3 [4]
 // ----------------------------------------------------------------------------------------------

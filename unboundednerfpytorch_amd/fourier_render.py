@@ -101,6 +101,11 @@ class FourierGridRenderer:
     DirectVoxGO forward (dvgo.py:306-425, rgbnet_direct) -- xyz_min / xyz_max are the scene box, rays are clipped against it
     and marched with their own step counts inside ugrid_render_march_dvgo (no contraction, no sample table); render kwargs
     `near` and `bg` as the reference, depth = sum w * step_id.  dvgo_render.DirectVoxGORenderer.render_rays builds it.
+    Optional `mpi` = {'mask', 'xyz2ijk_scale', 'xyz2ijk_shift', 'act_shift' [mpi_depth]} with fourier_freq_num = 0 and act_shift = 0:
+    the forward-facing DirectMPIGO forward (dmpigo.py:224-338) -- NDC rays, xyz_min / xyz_max the NDC box, every ray marched with
+    the same int((mpi_depth - 1) / stepsize) + 1 samples inside ugrid_render_march_mpi, the per-plane shift added to the density,
+    interval = stepsize * voxel_size_ratio in double (a Python float product), `bg` honoured, depth = sum w * (step + 0.5) / n.
+    mpi_render.DirectMPIGORenderer builds it.
     """
 
     def __init__(self, state, device, max_ws_bytes=48 << 30, pipeline=0, mlp_mode=None):
@@ -152,9 +157,21 @@ class FourierGridRenderer:
                        "scale": [float(x) for x in d["xyz2ijk_scale"]], "shift": [float(x) for x in d["xyz2ijk_shift"]]}
             if self.dv["mask"].dim() != 3:
                 raise RuntimeError("dvgo mask must be a [mx,my,mz] bool grid")
-        elif self.F == 0 and self.dc is None:
-            raise RuntimeError("fourier_freq_num = 0 is the DirectContractedVoxGO / DirectVoxGO path: pass state['dcvgo'] "
-                               "or state['dvgo']")
+        self.mp = None
+        if state.get("mpi") is not None:
+            if self.F != 0 or self.dc is not None or self.dv is not None:
+                raise RuntimeError("the DirectMPIGO march is for single-level grids (fourier_freq_num = 0), without 'dcvgo' / 'dvgo'")
+            d = state["mpi"]
+            self.mp = {"mask": d["mask"].to(dev).to(torch.bool).contiguous(),
+                       "scale": [float(x) for x in d["xyz2ijk_scale"]], "shift": [float(x) for x in d["xyz2ijk_shift"]],
+                       "act_shift": torch.as_tensor(d["act_shift"]).to(dev, torch.float32).reshape(-1).contiguous()}
+            if self.mp["mask"].dim() != 3:
+                raise RuntimeError("mpi mask must be a [mx,my,mz] bool grid")
+            if self.mp["act_shift"].numel() != self.G[2] or not 2 <= self.G[2] <= 256:
+                raise RuntimeError("mpi act_shift must hold one value per plane of the grid's z axis (2..256 planes)")
+        if self.F == 0 and self.dc is None and self.dv is None and self.mp is None:
+            raise RuntimeError("fourier_freq_num = 0 is the DirectContractedVoxGO / DirectVoxGO / DirectMPIGO path: pass "
+                               "state['dcvgo'], state['dvgo'] or state['mpi']")
         if self.thres <= 0:
             raise RuntimeError("fast_color_thres must be > 0 (the reference forward is not usable at 0 either, "
                                "FourierGrid_model.py:600-614)")
@@ -213,8 +230,14 @@ class FourierGridRenderer:
         # python float * 0-d fp32 tensor -> fp32 product (dvgo.py:319)
         return float(stepsize * torch.as_tensor(self.dv["voxel_size"], dtype=torch.float32))
 
+    def mpi_steps(self, stepsize):
+        """samples per ray of the DirectMPIGO march: int((mpi_depth - 1) / stepsize) + 1 (dmpigo.py:241)"""
+        return int((self.G[2] - 1) / stepsize) + 1
+
     def tables(self, stepsize):
         key = float(stepsize)
+        if self.mp is not None:
+            return None, None, self.mpi_steps(stepsize)
         if self.dv is not None:
             # no sample table: S = an upper bound of a ray's step count, ceil(box diagonal / stepdist) + 1 (sizes the work list)
             ext = [self._vec["xyz_max"][i] - self._vec["xyz_min"][i] for i in range(3)]
@@ -226,6 +249,8 @@ class FourierGridRenderer:
         return self._tables[key]
 
     def interval(self, stepsize):
+        if self.mp is not None:      # python float * python float (dmpigo.py:259), rounded to fp32 where Raw2Alpha takes it
+            return float(stepsize * self.voxel_size_ratio)
         # python float * 0-d fp32 tensor -> fp32 product (FourierGrid_model.py:572)
         return float(torch.tensor(self.voxel_size_ratio, dtype=torch.float32) * stepsize)
 
@@ -377,10 +402,20 @@ class FourierGridRenderer:
                 dvp.xyz2ijk_scale[i], dvp.xyz2ijk_shift[i] = self.dv["scale"][i], self.dv["shift"][i]
             dvp.near_clip, dvp.far_clip = float(render_kwargs["near"]), 1e9       # dvgo.py:318: the given far is ignored
             dvp.stepdist = self.stepdist(stepsize)
+        mpp = None
+        if self.mp is not None:
+            if float(render_kwargs.get("near", 0)) != 0 or float(render_kwargs.get("far", 1)) != 1:
+                raise ValueError("DirectMPIGO renders NDC rays with near = 0, far = 1 (dmpigo.py:237)")
+            mpp = _lib.MpiParams()
+            mpp.mask = self.mp["mask"].data_ptr()
+            mpp.mask_x, mpp.mask_y, mpp.mask_z = [int(x) for x in self.mp["mask"].shape]
+            for i in range(3):
+                mpp.xyz2ijk_scale[i], mpp.xyz2ijk_shift[i] = self.mp["scale"][i], self.mp["shift"][i]
+            mpp.mpi_depth, mpp.n_steps = self.G[2], S
         timing = render_kwargs.get("timing")  # optional list collecting ([ev0, ev1, ev2], n_rays) per launch group
         with _lib.guard(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            if self.pipeline > 1 and R >= 64 * 64 * self.pipeline and self.dc is None and self.dv is None:
+            if self.pipeline > 1 and R >= 64 * 64 * self.pipeline and self.dc is None and self.dv is None and self.mp is None:
                 self._forward_pipelined(rays_o, rays_d, viewdirs, t_tab, s_tab, S, stepsize, last, depth, rgb, timing)
             else:
                 chunk = self.rays_per_chunk(S)
@@ -400,6 +435,10 @@ class FourierGridRenderer:
                     elif dvp is not None:
                         _lib.check(_L.ugrid_render_march_dvgo(p, ctypes.byref(dvp), _p(o_), _p(d_), _p(self.density_bricks),
                                                               _p(last[b:e]), _p(depth[b:e]), _p(ws), st), "render_march_dvgo")
+                    elif mpp is not None:
+                        _lib.check(_L.ugrid_render_march_mpi(p, ctypes.byref(mpp), _p(o_), _p(d_), _p(self.density_bricks),
+                                                             _p(self.mp["act_shift"]), _p(last[b:e]), _p(depth[b:e]), _p(ws), st),
+                                   "render_march_mpi")
                     else:
                         _lib.check(_L.ugrid_render_march(p, _p(o_), _p(d_), _p(t_tab), _p(s_tab), _p(self.density_bricks),
                                                          _p(last[b:e]), _p(depth[b:e]), _p(ws), st), "render_march")
@@ -414,8 +453,8 @@ class FourierGridRenderer:
         out = {"alphainv_last": last, "rgb_marched": rgb, "n_max": S}
         if self.dc is not None:
             out["wsum_mid"] = wmid
-        if (self.dc is not None or self.dv is not None) and "bg" in render_kwargs:
-            rgb += last.unsqueeze(-1) * render_kwargs["bg"]   # dcvgo.py:349-352 / dvgo.py:405: rgb_marched += alphainv_last * bg
+        if (self.dc is not None or self.dv is not None or self.mp is not None) and "bg" in render_kwargs:
+            rgb += last.unsqueeze(-1) * render_kwargs["bg"]   # dcvgo.py:349-352 / dvgo.py:405 / dmpigo.py:314: rgb_marched += alphainv_last * bg
         if render_kwargs.get("render_depth", False):
             out["depth"] = depth
         return out
@@ -520,19 +559,19 @@ class FourierGridRenderer:
         return cls(state_from_reference_checkpoint(ckpt), device, **kw)
 
 
-def render_view_of(render_rays, device, H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, **render_kwargs):
+def render_view_of(render_rays, device, H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, ndc=False, **render_kwargs):
     """One whole view through a per-ray renderer (`render_rays(rays_o, rays_d, viewdirs, **render_kwargs)` -> dict of per-ray
     tensors: the bounded / contracted VoxGO renderers' fused paths): rays generated on the device in 8 x 8 pixel blocks, one
     pass, results put back in image order -- the body of the reference's render loop (run_render.py:41-70) without its 8192-ray
-    chunks.  Returns {key: [H,W(,3)]} on the device."""
+    chunks.  ndc: forward-facing NDC rays (DirectMPIGO).  Returns {key: [H,W(,3)]} on the device."""
     dev = torch.device(device)
     c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
     order = pixel_tile_order(H, W, dev)
     if order is not None:
-        ro, rd, vd = get_rays_of_pixel_index(H, W, K, c2w, order, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y)
+        ro, rd, vd = get_rays_of_pixel_index(H, W, K, c2w, order, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, ndc=ndc)
         out = render_rays(ro, rd, vd, ray_order="coherent", **render_kwargs)
         return {k: untile(v, H, W).reshape(H, W, *v.shape[1:]) for k, v in out.items() if torch.is_tensor(v)}
-    ro, rd, vd = get_rays_of_a_view(H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y)
+    ro, rd, vd = get_rays_of_a_view(H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, ndc=ndc)
     out = render_rays(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), vd.reshape(-1, 3).contiguous(), **render_kwargs)
     return {k: v.reshape(H, W, *v.shape[1:]) for k, v in out.items() if torch.is_tensor(v)}
 
@@ -708,8 +747,9 @@ def get_rays_of_pixels(ii, jj, K, c2w, inverse_y=False):
     return rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous()
 
 
-def _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, pixel_index=None):
-    """One-kernel ray generation (ugrid_rays_of_a_view) for a device-resident camera pose."""
+def _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, pixel_index=None, ndc=False):
+    """One-kernel ray generation (ugrid_rays_of_a_view, or ugrid_rays_of_a_view_ndc with near = 1 like dvgo.py:558) for a
+    device-resident camera pose."""
     if mode not in ("center", "lefttop"):
         raise NotImplementedError(mode)
     K9 = (ctypes.c_float * 9)(*[float(x) for x in (K.reshape(-1).tolist() if torch.is_tensor(K) else
@@ -721,29 +761,37 @@ def _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, pixel_index=None
     d = torch.empty(n, 3, dtype=torch.float32, device=dev)
     v = torch.empty(n, 3, dtype=torch.float32, device=dev)
     with _lib.guard(dev):
-        _lib.check(_L.ugrid_rays_of_a_view(H, W, ctypes.cast(K9, ctypes.c_void_p), _p(c2w), int(bool(inverse_y)), int(bool(flip_x)),
-                                           int(bool(flip_y)), int(mode == "center"), _p(pixel_index), n, _p(o), _p(d), _p(v),
-                                           torch.cuda.current_stream(dev).cuda_stream), "rays_of_a_view")
+        if ndc:
+            _lib.check(_L.ugrid_rays_of_a_view_ndc(H, W, ctypes.cast(K9, ctypes.c_void_p), _p(c2w), int(bool(inverse_y)),
+                                                   int(bool(flip_x)), int(bool(flip_y)), int(mode == "center"), _p(pixel_index), n,
+                                                   1.0, _p(o), _p(d), _p(v), torch.cuda.current_stream(dev).cuda_stream),
+                       "rays_of_a_view_ndc")
+        else:
+            _lib.check(_L.ugrid_rays_of_a_view(H, W, ctypes.cast(K9, ctypes.c_void_p), _p(c2w), int(bool(inverse_y)), int(bool(flip_x)),
+                                               int(bool(flip_y)), int(mode == "center"), _p(pixel_index), n, _p(o), _p(d), _p(v),
+                                               torch.cuda.current_stream(dev).cuda_stream), "rays_of_a_view")
     return o, d, v
 
 
-def get_rays_of_pixel_index(H, W, K, c2w, pixel_index, inverse_y=False, flip_x=False, flip_y=False, mode="center"):
+def get_rays_of_pixel_index(H, W, K, c2w, pixel_index, inverse_y=False, flip_x=False, flip_y=False, mode="center", ndc=False):
     """Rays of the listed flat pixel indices j*W+i (int64, on c2w's device) of a view: [n,3] each -- a rank's shard of a
     frame in one launch; bit-identical to the corresponding rows of get_rays_of_a_view."""
     if not c2w.is_cuda:
-        o, d, v = get_rays_of_a_view(H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, mode=mode)
+        o, d, v = get_rays_of_a_view(H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, mode=mode, ndc=ndc)
         return o.reshape(-1, 3)[pixel_index], d.reshape(-1, 3)[pixel_index], v.reshape(-1, 3)[pixel_index]
-    return _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, pixel_index.contiguous())
+    return _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, pixel_index.contiguous(), ndc=ndc)
 
 
-def get_rays_of_a_view(H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, mode="center"):
+def get_rays_of_a_view(H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, mode="center", ndc=False):
     """Pinhole rays of one view, pixel centres (+0.5): rays_o, rays_d, viewdirs, each [H,W,3], on c2w's
-    device.  Same conventions as the reference (dvgo.py:493-521,554-559; no NDC).  Device-resident pose: one HIP
+    device.  Same conventions as the reference (dvgo.py:493-521,554-559); ndc=True: rays_o / rays_d in the forward-facing
+    NDC space (ndc_rays with near = 1, dvgo.py:534-558), viewdirs still the world directions.  Device-resident pose: one HIP
     kernel; host tensors: the torch elementwise chain (host-side utility for tests and data preparation)."""
     if c2w.is_cuda:
-        o, d, v = _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode)
+        o, d, v = _rays_native(H, W, K, c2w, inverse_y, flip_x, flip_y, mode, ndc=ndc)
         return o.view(H, W, 3), d.view(H, W, 3), v.view(H, W, 3)
     dev = c2w.device
+    focal = float(K[0][0])      # (ndc_rays takes the caller's K[0][0] as a Python number)
     K = torch.as_tensor(K, dtype=torch.float32, device=dev)
     jj, ii = torch.meshgrid(torch.linspace(0, H - 1, H, device=dev), torch.linspace(0, W - 1, W, device=dev),
                             indexing="ij")
@@ -762,4 +810,19 @@ def get_rays_of_a_view(H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False
     rays_d = torch.sum(dirs[..., None, :] * c2w[:3, :3], -1)
     rays_o = c2w[:3, 3].expand(rays_d.shape)
     viewdirs = rays_d / rays_d.norm(dim=-1, keepdim=True)
+    if ndc:
+        rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
     return rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous()
+
+
+def ndc_rays(H, W, focal, near, rays_o, rays_d):
+    """World rays -> forward-facing NDC rays (dvgo.py:534-551), the reference's torch chain"""
+    t = -(near + rays_o[..., 2]) / rays_d[..., 2]
+    rays_o = rays_o + t[..., None] * rays_d
+    o0 = -1. / (W / (2. * focal)) * rays_o[..., 0] / rays_o[..., 2]
+    o1 = -1. / (H / (2. * focal)) * rays_o[..., 1] / rays_o[..., 2]
+    o2 = 1. + 2. * near / rays_o[..., 2]
+    d0 = -1. / (W / (2. * focal)) * (rays_d[..., 0] / rays_d[..., 2] - rays_o[..., 0] / rays_o[..., 2])
+    d1 = -1. / (H / (2. * focal)) * (rays_d[..., 1] / rays_d[..., 2] - rays_o[..., 1] / rays_o[..., 2])
+    d2 = -2. * near / rays_o[..., 2]
+    return torch.stack([o0, o1, o2], -1), torch.stack([d0, d1, d2], -1)
