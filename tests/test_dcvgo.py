@@ -85,7 +85,7 @@ def test_dcvgo_fused_render_matches_reference_golden(case, golden_dir):
     rend = DirectContractedVoxGORenderer(state, "cuda:0")
     assert rend.fused_supported()
     out = rend.render_rays(o, d, v, stepsize=0.5, bg=1, render_depth=True)
-    assert rend._fused is not None and rend._fused.dc is not None                # it really took the fused kernels
+    assert rend._fused is not None and rend._fused.variant == 'dcvgo'               # it really took the fused kernels
     for k in ("alphainv_last", "rgb_marched", "depth", "wsum_mid"):
         assert out[k].shape == gold[k].shape, k
         np.testing.assert_allclose(out[k].cpu().numpy(), gold[k], rtol=0, atol=1e-4, err_msg=k)

@@ -3,7 +3,8 @@
 
 Compiles csrc/ugrid_march.hip for gfx950 with line tables (-gline-tables-only: the code is the shipped -O3 code, the .loc
 directives only annotate it), takes the sample loop of one k_march instantiation (default k_march<3,false,6>: the S1 headline) and
-attributes every instruction to the source function its .loc points into -- and, inside ug_march_tile itself, to the statement:
+attributes every instruction to the source function its .loc points into -- the shared leaf helpers of ugrid_render.h
+(ug_normalise, ug_append_survivors, ...) by NAME -- and, for what ug_march_tile itself still writes out, to the statement:
 
     position | contraction | normalise (u) | level coordinates (sin / cos) | axis set-up | brick address | cell polynomial |
     level sum + mean | alpha | compositing (w, T, thresholds) | compaction | loop control
@@ -20,13 +21,14 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "unboundednerfpytorch_amd", "csrc")
 
-# statement classes inside ug_march_tile (first match wins), on the text of the source line
+# statement classes inside ug_march_tile (first match wins), on the text of the source line; a line that calls a leaf helper
+# (argument set-up) goes to the helper's phase
 TILE_RULES = [
-    (r"__ballot\(surv\)|mbcnt|ent\[idx\]|slot\[idx\]|nsurv", "compaction"),
+    (r"ug_append_survivors|nsurv", "compaction"),
     (r"__ballot\(!done\)|for \(int j", "loop control"),
     (r"t_table\[j\]|ox \+ dx \* t", "position"),
     (r"nrm|ug_rcp_refined|\* sc|a\.B - rn", "contraction"),
-    (r"a\.lox|a\.loy|a\.loz", "normalise (u)"),
+    (r"ug_normalise|float ux, uy, uz", "normalise (u)"),
     (r"ug_sincos|\(float\)\(1 << k\)", "level coordinates (sin / cos)"),
     (r"ug_div_r\(dens", "level sum + mean"),
     (r"ug_density_level|dens \+=", "level sum + mean"),
@@ -39,6 +41,9 @@ FUNC_PHASE = {
     "ug_axis_inrange": "axis set-up", "ug_alpha": "alpha",
     "ug_rcp_refined": "division helpers (contraction, u, mean, alpha)", "ug_div_r": "division helpers (contraction, u, mean, alpha)",
     "ug_norm3_torch": "contraction", "ug_lane": "compaction",
+    # the leaf helpers shared by the three tile functions
+    "ug_append_survivors": "compaction", "ug_normalise": "normalise (u)", "ug_composite": "compositing (w, T, thresholds)",
+    "ug_mask_lookup": "mask cache", "ug_outside_box": "mask cache",
 }
 
 

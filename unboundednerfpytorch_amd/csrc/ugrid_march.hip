@@ -348,22 +348,10 @@ struct ug_train_args {
 //   2 = DirectVoxGO (dvgo.py:306-400): per-ray box clipping and step count (infer_t_minmax / infer_n_samples /
 //       sample_pts_on_rays, render_utils_kernel.cu:16-57,100-260), mask_outbbox, the mask cache; a.S = slots per ray (>= the
 //       longest possible ray: the host sizes it for the box diagonal), t_table unused
-struct ug_train_vox {
-  const uint8_t *mask;
-  int32_t mi, mj, mk;
-  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+struct ug_train_vox : ug_mask_args {      // the mask cache: ug_mask_lookup (ugrid_render.h), shared with the render march
   float dist_thres;                 // mode 1
   float near, far, stepdist;        // mode 2
 };
-
-// mask cache: nearest voxel, C round(), NaN -> 0 like the device conversion (k_maskcache)
-__device__ __forceinline__ bool ug_train_maskcache(const ug_train_vox &v, float px, float py, float pz) {
-  float fi = roundf(px * v.sx + v.hx), fj = roundf(py * v.sy + v.hy), fk = roundf(pz * v.sz + v.hz);
-  fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
-  if (fi >= 0.f && fi < (float)v.mi && fj >= 0.f && fj < (float)v.mj && fk >= 0.f && fk < (float)v.mk)
-    return v.mask[((int64_t)fi * v.mj + (int64_t)fj) * v.mk + (int64_t)fk] != 0;
-  return false;
-}
 
 // sample t of a normalised ray, contracted outside the unit cube / ball (dcvgo.py:251-262, the arithmetic of k_train_march);
 // returns the norm before the contraction
@@ -570,7 +558,7 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
         keep = !((lox > px) | (loy > py) | (loz > pz) | (hix < px) | (hiy < py) | (hiz < pz));   // ~mask_outbbox
       }
     }
-    if (keep) keep = ug_train_maskcache(v, px, py, pz);
+    if (keep) keep = ug_mask_lookup(v, px, py, pz);
     if (keep) {
       const float ux = ug_unorm(px, lox, hix), uy = ug_unorm(py, loy, hiy), uz = ug_unorm(pz, loz, hiz);
       const ug_taps tp = ug_tap_setup_ld(a.X, a.Y, a.Z, ux, uy, uz);
@@ -804,13 +792,9 @@ extern "C" int ugrid_train_sample_compact(int64_t n_rays, int32_t n_samples, flo
 
 static int ug_fill_train_vox(ug_train_vox *v, const uint8_t *mask, const int32_t *mask_dims3, const float *xyz2ijk_scale3,
                              const float *xyz2ijk_shift3) {
-  if (!mask || !mask_dims3 || !xyz2ijk_scale3 || !xyz2ijk_shift3) return (int)hipErrorInvalidValue;
-  v->mask = mask;
-  v->mi = mask_dims3[0]; v->mj = mask_dims3[1]; v->mk = mask_dims3[2];
-  v->sx = xyz2ijk_scale3[0]; v->sy = xyz2ijk_scale3[1]; v->sz = xyz2ijk_scale3[2];
-  v->hx = xyz2ijk_shift3[0]; v->hy = xyz2ijk_shift3[1]; v->hz = xyz2ijk_shift3[2];
+  if (!mask_dims3) return (int)hipErrorInvalidValue;
   v->dist_thres = 0.f; v->near = 0.f; v->far = 0.f; v->stepdist = 1.f;
-  return 0;
+  return ug_fill_mask_args(*v, mask, mask_dims3[0], mask_dims3[1], mask_dims3[2], xyz2ijk_scale3, xyz2ijk_shift3);
 }
 
 extern "C" int ugrid_train_sample_dcvgo(const float *density_grid, int X, int Y, int Z, const float *rays_o, const float *rays_d,
@@ -904,19 +888,37 @@ extern "C" int ugrid_train_compact(int64_t n_rays, int32_t n_samples, const floa
   return 0;
 }
 
+// block -> tile of the four march kernels (256 threads = 4 waves = 4 consecutive tiles, blocks spread over the XCDs by
+// ug_xcd_remap): a wave that has a tile runs march(tile, ent, slot) -> the tile's survivor count on it and records the count
+template <class MarchTile>
+__device__ __forceinline__ void ug_march_block(const ug_ws_view &ws, int64_t nblocks, MarchTile march) {
+  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
+  if (blk >= nblocks) return;
+  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
+  if (tile >= ws.n_tiles) return;
+  const int n = march(tile, ws.ent + tile * ws.cap, ws.slot + tile * ws.cap);
+  if (ug_lane() == 0) ws.count[tile] = n;
+}
+
+// launch geometry of the four march kernels: the work-list view, 4 tiles per block, the grid rounded up to the 8 XCDs
+struct ug_march_geom { ug_ws_view ws; int64_t nblocks; dim3 grid; };
+static inline ug_march_geom ug_march_geometry(void *ws_mem, int64_t n_rays, int32_t S) {
+  ug_march_geom g;
+  g.ws = ug_ws_make(ws_mem, n_rays, S);
+  g.nblocks = (g.ws.n_tiles + 3) / 4;
+  g.grid = dim3((unsigned)(((g.nblocks + 7) / 8) * 8));  // room for the XCD remap
+  return g;
+}
+
 template <int F, bool L2, int W>
 __global__ void __launch_bounds__(256, W)
 k_march(ug_march_args a, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
         const float *__restrict__ t_table, const float *__restrict__ s_table,
         const float *__restrict__ bricks, float *__restrict__ alphainv_last, float *__restrict__ depth,
         ug_ws_view ws, int64_t nblocks) {
-  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
-  if (blk >= nblocks) return;
-  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
-  if (tile >= ws.n_tiles) return;
-  const int n = ug_march_tile<F, L2>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile,
-                                     ws.ent + tile * ws.cap, ws.slot + tile * ws.cap);
-  if (ug_lane() == 0) ws.count[tile] = n;
+  ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
+    return ug_march_tile<F, L2>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile, ent, slot);
+  });
 }
 
 
@@ -927,13 +929,9 @@ k_march_dcvgo(ug_march_args a, ug_dc_args dc, const float *__restrict__ rays_o, 
               const float *__restrict__ t_table, const float *__restrict__ s_table, const float *__restrict__ bricks,
               float *__restrict__ alphainv_last, float *__restrict__ depth, float *__restrict__ wsum_mid, ug_ws_view ws,
               int64_t nblocks) {
-  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
-  if (blk >= nblocks) return;
-  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
-  if (tile >= ws.n_tiles) return;
-  const int n = ug_march_tile<0, L2, true>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile,
-                                           ws.ent + tile * ws.cap, ws.slot + tile * ws.cap, dc, wsum_mid);
-  if (ug_lane() == 0) ws.count[tile] = n;
+  ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
+    return ug_march_tile<0, L2, true>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile, ent, slot, dc, wsum_mid);
+  });
 }
 
 // bounded DirectVoxGO march (ug_march_tile_dvgo): variable-length rays clipped against the scene box
@@ -941,13 +939,9 @@ __global__ void __launch_bounds__(256, 6)
 k_march_dvgo(ug_march_args a, ug_dv_args dv, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
              const float *__restrict__ bricks, float *__restrict__ alphainv_last, float *__restrict__ depth, ug_ws_view ws,
              int64_t nblocks) {
-  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
-  if (blk >= nblocks) return;
-  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
-  if (tile >= ws.n_tiles) return;
-  const int n = ug_march_tile_dvgo(a, dv, rays_o, rays_d, bricks, alphainv_last, depth, tile, ws.ent + tile * ws.cap,
-                                   ws.slot + tile * ws.cap, a.S);
-  if (ug_lane() == 0) ws.count[tile] = n;
+  ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
+    return ug_march_tile_dvgo(a, dv, rays_o, rays_d, bricks, alphainv_last, depth, tile, ent, slot, a.S);
+  });
 }
 
 // forward-facing DirectMPIGO march (ug_march_tile_mpi): NDC rays, n samples each; act_shift [D <= 256] staged in LDS
@@ -958,13 +952,9 @@ k_march_mpi(ug_march_args a, ug_mpi_args mp, const float *__restrict__ rays_o, c
   __shared__ float shift[256];
   if ((int)threadIdx.x < mp.D) shift[threadIdx.x] = act_shift[threadIdx.x];
   __syncthreads();
-  const int64_t blk = ug_xcd_remap(blockIdx.x, nblocks);
-  if (blk >= nblocks) return;
-  const int64_t tile = blk * 4 + (threadIdx.x >> 6);
-  if (tile >= ws.n_tiles) return;
-  const int n = ug_march_tile_mpi(a, mp, rays_o, rays_d, bricks, shift, alphainv_last, depth, tile, ws.ent + tile * ws.cap,
-                                  ws.slot + tile * ws.cap);
-  if (ug_lane() == 0) ws.count[tile] = n;
+  ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
+    return ug_march_tile_mpi(a, mp, rays_o, rays_d, bricks, shift, alphainv_last, depth, tile, ent, slot);
+  });
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1079,16 +1069,14 @@ extern "C" int ug_set_march_waves(int w) { if (w < 4 || w > 6) return 1; g_march
 template <int F, int W>
 static int ug_march_launch_w(const ugrid_render_params *p, const ug_march_args &a, const float *rays_o,
                              const float *rays_d, const float *t_table, const float *s_table,
-                             const float *bricks, float *alphainv_last, float *depth, ug_ws_view ws,
+                             const float *bricks, float *alphainv_last, float *depth, const ug_march_geom &g,
                              hipStream_t st) {
-  const int64_t nblocks = (ws.n_tiles + 3) / 4;
-  const int64_t grid = ((nblocks + 7) / 8) * 8;  // room for the XCD remap
   if (p->norm_l2)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, true, W>), dim3((unsigned)grid), dim3(256), 0, st, a, rays_o,
-                       rays_d, t_table, s_table, bricks, alphainv_last, depth, ws, nblocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, true, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                       rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, false, W>), dim3((unsigned)grid), dim3(256), 0, st, a, rays_o,
-                       rays_d, t_table, s_table, bricks, alphainv_last, depth, ws, nblocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, false, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                       rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
   UG_LAUNCH_CHECK();
   return 0;
 }
@@ -1096,12 +1084,12 @@ static int ug_march_launch_w(const ugrid_render_params *p, const ug_march_args &
 template <int F>
 static int ug_march_launch(const ugrid_render_params *p, const ug_march_args &a, const float *rays_o,
                            const float *rays_d, const float *t_table, const float *s_table,
-                           const float *bricks, float *alphainv_last, float *depth, ug_ws_view ws,
+                           const float *bricks, float *alphainv_last, float *depth, const ug_march_geom &g,
                            hipStream_t st) {
   switch (g_march_waves) {
-    case 4: return ug_march_launch_w<F, 4>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, ws, st);
-    case 6: return ug_march_launch_w<F, 6>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, ws, st);
-    default: return ug_march_launch_w<F, 5>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, ws, st);
+    case 4: return ug_march_launch_w<F, 4>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
+    case 6: return ug_march_launch_w<F, 6>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
+    default: return ug_march_launch_w<F, 5>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
   }
 }
 
@@ -1112,13 +1100,13 @@ extern "C" int ugrid_render_march(const ugrid_render_params *p, const float *ray
   ug_march_args a;
   const int rc = ug_fill_march_args(p, a);
   if (rc) return rc;
-  ug_ws_view ws = ug_ws_make(ws_mem, p->n_rays, p->n_samples);
+  const ug_march_geom g = ug_march_geometry(ws_mem, p->n_rays, p->n_samples);
   switch (p->freq_num) {
-    case 1: return ug_march_launch<1>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, ws, ST(s));
-    case 2: return ug_march_launch<2>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, ws, ST(s));
-    case 3: return ug_march_launch<3>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, ws, ST(s));
-    case 4: return ug_march_launch<4>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, ws, ST(s));
-    case 5: return ug_march_launch<5>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, ws, ST(s));
+    case 1: return ug_march_launch<1>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, g, ST(s));
+    case 2: return ug_march_launch<2>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, g, ST(s));
+    case 3: return ug_march_launch<3>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, g, ST(s));
+    case 4: return ug_march_launch<4>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, g, ST(s));
+    case 5: return ug_march_launch<5>(p, a, rays_o, rays_d, t_table, s_table, density_bricks, alphainv_last, depth, g, ST(s));
     default: return (int)hipErrorInvalidValue;
   }
 }
@@ -1129,24 +1117,20 @@ extern "C" int ugrid_render_march_dcvgo(const ugrid_render_params *p, const ugri
                                         const float *density_bricks, float *alphainv_last, float *depth, float *wsum_mid,
                                         void *ws_mem, ugrid_stream_t s) {
   if (p->n_rays <= 0) return 0;
-  if (p->freq_num != 0 || !q || !q->mask || q->mask_x < 1 || q->mask_y < 1 || q->mask_z < 1) return (int)hipErrorInvalidValue;
+  if (p->freq_num != 0 || !q) return (int)hipErrorInvalidValue;
   ug_march_args a;
-  const int rc = ug_fill_march_args(p, a);
-  if (rc) return rc;
   ug_dc_args dc;
-  dc.mask = q->mask; dc.mi = q->mask_x; dc.mj = q->mask_y; dc.mk = q->mask_z;
-  dc.sx = q->xyz2ijk_scale[0]; dc.sy = q->xyz2ijk_scale[1]; dc.sz = q->xyz2ijk_scale[2];
-  dc.hx = q->xyz2ijk_shift[0]; dc.hy = q->xyz2ijk_shift[1]; dc.hz = q->xyz2ijk_shift[2];
+  int rc = ug_fill_mask_args(dc, q->mask, q->mask_x, q->mask_y, q->mask_z, q->xyz2ijk_scale, q->xyz2ijk_shift);
+  if (!rc) rc = ug_fill_march_args(p, a);
+  if (rc) return rc;
   dc.dist_thres = q->dist_thres;
-  ug_ws_view ws = ug_ws_make(ws_mem, p->n_rays, p->n_samples);
-  const int64_t nblocks = (ws.n_tiles + 3) / 4;
-  const int64_t grid = ((nblocks + 7) / 8) * 8;  // room for the XCD remap
+  const ug_march_geom g = ug_march_geometry(ws_mem, p->n_rays, p->n_samples);
   if (p->norm_l2)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_dcvgo<true>), dim3((unsigned)grid), dim3(256), 0, ST(s), a, dc, rays_o, rays_d, t_table,
-                       s_table, density_bricks, alphainv_last, depth, wsum_mid, ws, nblocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_dcvgo<true>), g.grid, dim3(256), 0, ST(s), a, dc, rays_o, rays_d, t_table,
+                       s_table, density_bricks, alphainv_last, depth, wsum_mid, g.ws, g.nblocks);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_dcvgo<false>), dim3((unsigned)grid), dim3(256), 0, ST(s), a, dc, rays_o, rays_d, t_table,
-                       s_table, density_bricks, alphainv_last, depth, wsum_mid, ws, nblocks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_dcvgo<false>), g.grid, dim3(256), 0, ST(s), a, dc, rays_o, rays_d, t_table,
+                       s_table, density_bricks, alphainv_last, depth, wsum_mid, g.ws, g.nblocks);
   UG_LAUNCH_CHECK();
   return 0;
 }
@@ -1156,21 +1140,16 @@ extern "C" int ugrid_render_march_dvgo(const ugrid_render_params *p, const ugrid
                                        const float *rays_d, const float *density_bricks, float *alphainv_last, float *depth,
                                        void *ws_mem, ugrid_stream_t s) {
   if (p->n_rays <= 0) return 0;
-  if (p->freq_num != 0 || !q || !q->mask || q->mask_x < 1 || q->mask_y < 1 || q->mask_z < 1 || !(q->stepdist > 0.f))
-    return (int)hipErrorInvalidValue;
+  if (p->freq_num != 0 || !q || !(q->stepdist > 0.f)) return (int)hipErrorInvalidValue;
   ug_march_args a;
-  const int rc = ug_fill_march_args(p, a);
-  if (rc) return rc;
   ug_dv_args dv;
-  dv.mask = q->mask; dv.mi = q->mask_x; dv.mj = q->mask_y; dv.mk = q->mask_z;
-  dv.sx = q->xyz2ijk_scale[0]; dv.sy = q->xyz2ijk_scale[1]; dv.sz = q->xyz2ijk_scale[2];
-  dv.hx = q->xyz2ijk_shift[0]; dv.hy = q->xyz2ijk_shift[1]; dv.hz = q->xyz2ijk_shift[2];
+  int rc = ug_fill_mask_args(dv, q->mask, q->mask_x, q->mask_y, q->mask_z, q->xyz2ijk_scale, q->xyz2ijk_shift);
+  if (!rc) rc = ug_fill_march_args(p, a);
+  if (rc) return rc;
   dv.near = q->near_clip; dv.far = q->far_clip; dv.stepdist = q->stepdist;
-  ug_ws_view ws = ug_ws_make(ws_mem, p->n_rays, p->n_samples);
-  const int64_t nblocks = (ws.n_tiles + 3) / 4;
-  const int64_t grid = ((nblocks + 7) / 8) * 8;  // room for the XCD remap
-  hipLaunchKernelGGL(k_march_dvgo, dim3((unsigned)grid), dim3(256), 0, ST(s), a, dv, rays_o, rays_d, density_bricks, alphainv_last,
-                     depth, ws, nblocks);
+  const ug_march_geom g = ug_march_geometry(ws_mem, p->n_rays, p->n_samples);
+  hipLaunchKernelGGL(k_march_dvgo, g.grid, dim3(256), 0, ST(s), a, dv, rays_o, rays_d, density_bricks, alphainv_last,
+                     depth, g.ws, g.nblocks);
   UG_LAUNCH_CHECK();
   return 0;
 }
@@ -1181,23 +1160,18 @@ extern "C" int ugrid_render_march_mpi(const ugrid_render_params *p, const ugrid_
                                       const float *rays_d, const float *density_bricks, const float *act_shift, float *alphainv_last,
                                       float *depth, void *ws_mem, ugrid_stream_t s) {
   if (p->n_rays <= 0) return 0;
-  if (p->freq_num != 0 || !q || !q->mask || q->mask_x < 1 || q->mask_y < 1 || q->mask_z < 1 || !act_shift)
-    return (int)hipErrorInvalidValue;
+  if (p->freq_num != 0 || !q || !act_shift) return (int)hipErrorInvalidValue;
   // the LDS table holds 256 planes; a lane's samples fill at most n_samples entries of its tile's survivor list
   if (q->mpi_depth < 2 || q->mpi_depth > 256 || q->n_steps < 2 || q->n_steps > p->n_samples) return (int)hipErrorInvalidValue;
   ug_march_args a;
-  const int rc = ug_fill_march_args(p, a);
-  if (rc) return rc;
   ug_mpi_args mp;
-  mp.mask = q->mask; mp.mi = q->mask_x; mp.mj = q->mask_y; mp.mk = q->mask_z;
-  mp.sx = q->xyz2ijk_scale[0]; mp.sy = q->xyz2ijk_scale[1]; mp.sz = q->xyz2ijk_scale[2];
-  mp.hx = q->xyz2ijk_shift[0]; mp.hy = q->xyz2ijk_shift[1]; mp.hz = q->xyz2ijk_shift[2];
+  int rc = ug_fill_mask_args(mp, q->mask, q->mask_x, q->mask_y, q->mask_z, q->xyz2ijk_scale, q->xyz2ijk_shift);
+  if (!rc) rc = ug_fill_march_args(p, a);
+  if (rc) return rc;
   mp.D = q->mpi_depth; mp.n = q->n_steps;
-  ug_ws_view ws = ug_ws_make(ws_mem, p->n_rays, p->n_samples);
-  const int64_t nblocks = (ws.n_tiles + 3) / 4;
-  const int64_t grid = ((nblocks + 7) / 8) * 8;  // room for the XCD remap
-  hipLaunchKernelGGL(k_march_mpi, dim3((unsigned)grid), dim3(256), 0, ST(s), a, mp, rays_o, rays_d, density_bricks, act_shift,
-                     alphainv_last, depth, ws, nblocks);
+  const ug_march_geom g = ug_march_geometry(ws_mem, p->n_rays, p->n_samples);
+  hipLaunchKernelGGL(k_march_mpi, g.grid, dim3(256), 0, ST(s), a, mp, rays_o, rays_d, density_bricks, act_shift,
+                     alphainv_last, depth, g.ws, g.nblocks);
   UG_LAUNCH_CHECK();
   return 0;
 }

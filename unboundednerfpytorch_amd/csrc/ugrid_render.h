@@ -194,15 +194,77 @@ __device__ __forceinline__ float ug_density_level(const char *__restrict__ lvl, 
   return fmaf(fmaf(p11, ty, p10), tx, fmaf(p01, ty, p00));
 }
 
+// ----------------------------------------------------------------------------------------------
+// leaves shared by the three tile functions below (and, for the mask cache, by the training samplers of ugrid_march.hip):
+// every rule that is a bit-exactness contract with the reference is written once, here
+// ----------------------------------------------------------------------------------------------
+// ((p - lo) / (hi - lo)) * 2 - 1 per axis
+__device__ __forceinline__ void ug_normalise(const ug_march_args &a, float px, float py, float pz, float &ux, float &uy, float &uz) {
+  ux = ug_div_r(px - a.lox, a.ex, a.irx) * 2.f - 1.f;
+  uy = ug_div_r(py - a.loy, a.ey, a.iry) * 2.f - 1.f;
+  uz = ug_div_r(pz - a.loz, a.ez, a.irz) * 2.f - 1.f;
+}
+
+// mask_outbbox of sample_pts_on_rays / sample_ndc_pts_on_rays (render_utils_kernel.cu:100-270)
+__device__ __forceinline__ bool ug_outside_box(const ug_march_args &a, float px, float py, float pz) {
+  return (a.lox > px) | (a.loy > py) | (a.loz > pz) | (a.hix < px) | (a.hiy < py) | (a.hiz < pz);
+}
+
+// mask cache (maskcache_lookup, render_utils_kernel.cu:374-392: nearest voxel of a bool grid)
+struct ug_mask_args {
+  const uint8_t *mask;
+  int32_t mi, mj, mk;
+  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+};
+
+// nearest voxel, C round(), NaN -> 0 like the device conversion (k_maskcache); false = known free space or outside the mask grid
+__device__ __forceinline__ bool ug_mask_lookup(const ug_mask_args &m, float px, float py, float pz) {
+  float fi = roundf(px * m.sx + m.hx), fj = roundf(py * m.sy + m.hy), fk = roundf(pz * m.sz + m.hz);
+  fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
+  if (fi >= 0.f && fi < (float)m.mi && fj >= 0.f && fj < (float)m.mj && fk >= 0.f && fk < (float)m.mk)
+    return m.mask[((int64_t)fi * m.mj + (int64_t)fj) * m.mk + (int64_t)fk] != 0;
+  return false;
+}
+
+static inline int ug_fill_mask_args(ug_mask_args &m, const uint8_t *mask, int32_t mask_x, int32_t mask_y, int32_t mask_z,
+                                    const float *scale3, const float *shift3) {
+  if (!mask || !scale3 || !shift3 || mask_x < 1 || mask_y < 1 || mask_z < 1) return (int)hipErrorInvalidValue;
+  m.mask = mask; m.mi = mask_x; m.mj = mask_y; m.mk = mask_z;
+  m.sx = scale3[0]; m.sy = scale3[1]; m.sz = scale3[2];
+  m.hx = shift3[0]; m.hy = shift3[1]; m.hz = shift3[2];
+  return 0;
+}
+
+// front-to-back compositing of one sample (Alphas2Weights, render_utils_kernel.cu: T in float, the product in double, early stop
+// below 1e-3): updates T / w / done, returns whether the sample survives both thresholds
+__device__ __forceinline__ bool ug_composite(float alpha, float thres, float &T, float &w, bool &done) {
+  if (!(alpha > thres)) return false;
+  w = T * alpha;
+  T = (float)((double)T * (1. - (double)alpha));
+  if ((double)T < 1e-3) done = true;
+  return w > thres;
+}
+
+// append the wave's surviving samples to its private list in lane order (ballot + mbcnt prefix: no atomics, deterministic)
+__device__ __forceinline__ void ug_append_survivors(bool surv, float px, float py, float pz, float w, int lane,
+                                                    float4 *__restrict__ ent, uint8_t *__restrict__ slot, int &nsurv) {
+  const unsigned long long m = __ballot(surv);
+  if (m != 0ull) {
+    if (surv) {
+      const int idx = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+      ent[idx] = make_float4(px, py, pz, w);
+      slot[idx] = (uint8_t)lane;
+    }
+    nsurv += __popcll(m);
+  }
+}
+
 // DirectContractedVoxGO additions to the march (dcvgo.py:228-310; DC = true, single-level grids, F = 0): of the contracted
 // samples only those are evaluated whose running inter-sample distance has just exceeded dist_thres (cumdist_thres,
 // ub360_utils_kernel.cu:24-31 -- the serial recurrence is a register of the lane that owns the ray), and only where the
 // mask cache (maskcache_lookup, render_utils_kernel.cu:374-392: nearest voxel of a bool grid) says "not known free space";
 // wsum_mid = sum of the weights of the surviving UN-contracted samples (dcvgo.py:354-358).
-struct ug_dc_args {
-  const uint8_t *mask;
-  int32_t mi, mj, mk;
-  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+struct ug_dc_args : ug_mask_args {
   float dist_thres;
 };
 
@@ -256,10 +318,8 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
         py = ug_div_r(py, nrm, rn) * sc;
         pz = ug_div_r(pz, nrm, rn) * sc;
       }
-      // ((p - lo) / (hi - lo)) * 2 - 1
-      const float ux = ug_div_r(px - a.lox, a.ex, a.irx) * 2.f - 1.f;
-      const float uy = ug_div_r(py - a.loy, a.ey, a.iry) * 2.f - 1.f;
-      const float uz = ug_div_r(pz - a.loz, a.ez, a.irz) * 2.f - 1.f;
+      float ux, uy, uz;
+      ug_normalise(a, px, py, pz, ux, uy, uz);
       bool keep = true;
       [[maybe_unused]] bool inner = true;
       if constexpr (DC) {
@@ -272,13 +332,7 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
           keep = keep || over;
         }
         ppx = px; ppy = py; ppz = pz;
-        if (keep) {       // mask cache: nearest voxel, C round(), NaN -> 0 like the device conversion (k_maskcache)
-          float fi = roundf(px * dc.sx + dc.hx), fj = roundf(py * dc.sy + dc.hy), fk = roundf(pz * dc.sz + dc.hz);
-          fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
-          keep = false;
-          if (fi >= 0.f && fi < (float)dc.mi && fj >= 0.f && fj < (float)dc.mj && fk >= 0.f && fk < (float)dc.mk)
-            keep = dc.mask[((int64_t)fi * dc.mj + (int64_t)fj) * dc.mk + (int64_t)fk] != 0;
-        }
+        if (keep) keep = ug_mask_lookup(dc, px, py, pz);
       }
       if (keep) {
         float dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
@@ -301,6 +355,9 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
         dens = ug_div_r(dens, (float)P, 1.0f / (float)P);   // mean over levels: Markstein division, 3 VALU instead of 10
         const float xs = dens + a.shift;
         const float alpha = ug_alpha(xs, a.interval);
+        // ug_composite, written out: inlining the helper here changes this kernel's register allocation throughout
+        // (k_march<3,false,6>: 80 -> 51 VGPRs, <3,false,5>: 85 -> 92), so the headline kernel keeps the statements its
+        // measured code was generated from.  The rule itself is ug_composite's; change both together.
         if (alpha > a.thres) {
           w = T * alpha;
           T = (float)((double)T * (1. - (double)alpha));
@@ -313,16 +370,7 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
         }
       }
     }
-    const unsigned long long m = __ballot(surv);
-    if (m != 0ull) {
-      if (surv) {
-        const int idx = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
-                                                          __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        ent[idx] = make_float4(px, py, pz, w);
-        slot[idx] = (uint8_t)lane;
-      }
-      nsurv += __popcll(m);
-    }
+    ug_append_survivors(surv, px, py, pz, w, lane, ent, slot, nsurv);
   }
   if (valid) {
     alphainv_last[ray] = T;
@@ -339,10 +387,7 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
 // the wave until its longest ray is done.  Points outside the box (mask_outbbox) and in known free space (mask cache)
 // are exec-masked before the brick load; depth = sum w * step_id (dvgo.py:419-423).
 // ----------------------------------------------------------------------------------------------
-struct ug_dv_args {
-  const uint8_t *mask;
-  int32_t mi, mj, mk;
-  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+struct ug_dv_args : ug_mask_args {
   float near, far, stepdist;
 };
 
@@ -383,40 +428,15 @@ __device__ __forceinline__ int ug_march_tile_dvgo(const ug_march_args &a, const 
     if (!done) {
       const float dist = dv.stepdist * (float)j;
       px = sx + dx * dist; py = sy + dy * dist; pz = sz + dz * dist;
-      bool keep = !((a.lox > px) | (a.loy > py) | (a.loz > pz) | (a.hix < px) | (a.hiy < py) | (a.hiz < pz));   // mask_outbbox
-      if (keep) {       // mask cache (k_maskcache semantics)
-        float fi = roundf(px * dv.sx + dv.hx), fj = roundf(py * dv.sy + dv.hy), fk = roundf(pz * dv.sz + dv.hz);
-        fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
-        keep = false;
-        if (fi >= 0.f && fi < (float)dv.mi && fj >= 0.f && fj < (float)dv.mj && fk >= 0.f && fk < (float)dv.mk)
-          keep = dv.mask[((int64_t)fi * dv.mj + (int64_t)fj) * dv.mk + (int64_t)fk] != 0;
-      }
-      if (keep) {
-        const float ux = ug_div_r(px - a.lox, a.ex, a.irx) * 2.f - 1.f;
-        const float uy = ug_div_r(py - a.loy, a.ey, a.iry) * 2.f - 1.f;
-        const float uz = ug_div_r(pz - a.loz, a.ez, a.irz) * 2.f - 1.f;
+      if (!ug_outside_box(a, px, py, pz) && ug_mask_lookup(dv, px, py, pz)) {
+        float ux, uy, uz;
+        ug_normalise(a, px, py, pz, ux, uy, uz);
         const float dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
-        const float alpha = ug_alpha(dens + a.shift, a.interval);
-        if (alpha > a.thres) {
-          w = T * alpha;
-          T = (float)((double)T * (1. - (double)alpha));
-          if (w > a.thres) {
-            surv = true;
-            dsum += w * (float)j;
-          }
-          if ((double)T < 1e-3) done = true;
-        }
+        surv = ug_composite(ug_alpha(dens + a.shift, a.interval), a.thres, T, w, done);
+        if (surv) dsum += w * (float)j;
       }
     }
-    const unsigned long long m = __ballot(surv);
-    if (m != 0ull) {
-      if (surv) {
-        const int idx = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        ent[idx] = make_float4(px, py, pz, w);
-        slot[idx] = (uint8_t)lane;
-      }
-      nsurv += __popcll(m);
-    }
+    ug_append_survivors(surv, px, py, pz, w, lane, ent, slot, nsurv);
   }
   if (valid) {
     alphainv_last[ray] = T;
@@ -435,10 +455,7 @@ __device__ __forceinline__ int ug_march_tile_dvgo(const ug_march_args &a, const 
 // added in fp32 like the reference's `self.density(p) + self.act_shift(p)`; Raw2Alpha then gets shift 0.
 // depth = sum w * (step + 0.5) / n (dmpigo.py:319: int64 + 0.5 promotes to fp32).
 // ----------------------------------------------------------------------------------------------
-struct ug_mpi_args {
-  const uint8_t *mask;
-  int32_t mi, mj, mk;
-  float sx, sy, sz, hx, hy, hz;     // xyz2ijk_scale / xyz2ijk_shift
+struct ug_mpi_args : ug_mask_args {
   int32_t D, n;                     // mpi_depth, samples per ray
 };
 
@@ -467,18 +484,9 @@ __device__ __forceinline__ int ug_march_tile_mpi(const ug_march_args &a, const u
     if (!done) {
       const float dist = (float)j / nm1;
       px = ox + rx * dist; py = oy + ry * dist; pz = oz + rz * dist;
-      bool keep = !((a.lox > px) | (a.loy > py) | (a.loz > pz) | (a.hix < px) | (a.hiy < py) | (a.hiz < pz));   // mask_outbbox
-      if (keep) {       // mask cache (k_maskcache semantics)
-        float fi = roundf(px * mp.sx + mp.hx), fj = roundf(py * mp.sy + mp.hy), fk = roundf(pz * mp.sz + mp.hz);
-        fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
-        keep = false;
-        if (fi >= 0.f && fi < (float)mp.mi && fj >= 0.f && fj < (float)mp.mj && fk >= 0.f && fk < (float)mp.mk)
-          keep = mp.mask[((int64_t)fi * mp.mj + (int64_t)fj) * mp.mk + (int64_t)fk] != 0;
-      }
-      if (keep) {
-        const float ux = ug_div_r(px - a.lox, a.ex, a.irx) * 2.f - 1.f;
-        const float uy = ug_div_r(py - a.loy, a.ey, a.iry) * 2.f - 1.f;
-        const float uz = ug_div_r(pz - a.loz, a.ez, a.irz) * 2.f - 1.f;
+      if (!ug_outside_box(a, px, py, pz) && ug_mask_lookup(mp, px, py, pz)) {
+        float ux, uy, uz;
+        ug_normalise(a, px, py, pz, ux, uy, uz);
         const float dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
         // act_shift: uz in [-1, 1] for a point inside the box, so iz in [0, D-1]
         const float iz = ((uz + 1.f) / 2.f) * dm1;
@@ -486,27 +494,11 @@ __device__ __forceinline__ int ug_march_tile_mpi(const ug_march_args &a, const u
         const int i0 = min(max((int)f0, 0), mp.D - 1);
         float sh = shift[i0] * ((f0 + 1.f) - iz);
         if (i0 + 1 < mp.D) sh = sh + shift[i0 + 1] * (iz - f0);
-        const float alpha = ug_alpha(dens + sh, a.interval);
-        if (alpha > a.thres) {
-          w = T * alpha;
-          T = (float)((double)T * (1. - (double)alpha));
-          if (w > a.thres) {
-            surv = true;
-            dsum += w * (((float)j + 0.5f) / nf);
-          }
-          if ((double)T < 1e-3) done = true;
-        }
+        surv = ug_composite(ug_alpha(dens + sh, a.interval), a.thres, T, w, done);
+        if (surv) dsum += w * (((float)j + 0.5f) / nf);
       }
     }
-    const unsigned long long m = __ballot(surv);
-    if (m != 0ull) {
-      if (surv) {
-        const int idx = nsurv + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        ent[idx] = make_float4(px, py, pz, w);
-        slot[idx] = (uint8_t)lane;
-      }
-      nsurv += __popcll(m);
-    }
+    ug_append_survivors(surv, px, py, pz, w, lane, ent, slot, nsurv);
   }
   if (valid) {
     alphainv_last[ray] = T;

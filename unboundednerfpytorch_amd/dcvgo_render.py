@@ -12,7 +12,8 @@ exist for tests: they let the same composition run against another implementatio
 (the CPU oracle); the default is the HIP library, which needs a GPU -- there is no CPU fallback.
 """
 import torch
-import torch.nn.functional as F
+
+from .bounded_render import BoundedRenderer
 
 
 def dcvgo_state_from_params(xyz_min, xyz_max, num_voxels, num_voxels_base, alpha_init, density_grid, k0_grid,
@@ -61,96 +62,31 @@ def dcvgo_state_from_reference_checkpoint(ckpt):
     return st
 
 
-class _HipOps:
-    """The product's extension modules + grid query, resolved lazily (importing them loads libugrid_hip.so)."""
+class DirectContractedVoxGORenderer(BoundedRenderer):
+    """render_rays: the whole chain of dcvgo.py:228-384 in two launches, no [N,S,3] point tensor, no boolean compactions;
+    render_kwargs as forward(): stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
+    output_keys = ('rgb_marched', 'depth', 'alphainv_last', 'wsum_mid')
 
-    def __init__(self):
-        from . import render_utils_cuda, ub360_utils_cuda
-        from .grid import grid_query
-        self.ru, self.ub, self.query = render_utils_cuda, ub360_utils_cuda, grid_query
-
-
-class DirectContractedVoxGORenderer:
     def __init__(self, state, device, ops=None, query=None):
-        dev = torch.device(device)
-        if ops is None:
-            if dev.type != "cuda":
-                raise RuntimeError("DirectContractedVoxGORenderer needs a HIP device (no CPU path)")
-            hip = _HipOps()
-            self.ru, self.ub, self.query = hip.ru, hip.ub, hip.query
-        else:                                   # tests: another implementation of the extension modules
-            self.ru, self.ub, self.query = ops.render_utils_cuda, ops.ub360_utils_cuda, query
-        self.device = dev
-        self.s = {k: (v.to(dev).contiguous() if torch.is_tensor(v) else
-                      ([x.to(dev).contiguous() for x in v] if isinstance(v, list) else v)) for k, v in state.items()}
-        self.viewfreq = torch.tensor([float(2 ** i) for i in range(int(state["viewbase_pe"]))], device=dev)
+        super().__init__(state, device, ops, query)
         self._tables = {}
-        self._fused = None if ops is None else False      # fused render kernels: HIP library only, built on first use
 
     @classmethod
     def from_reference_checkpoint(cls, ckpt, device):
         """ckpt: the dict the reference saves for a DirectContractedVoxGO model (torch.load('fine_last.tar', weights_only=False))"""
         return cls(dcvgo_state_from_reference_checkpoint(ckpt), device)
 
-    # -- fused inference path ----------------------------------------------------------------------------------
-    def fused_supported(self):
-        """the fused march (ugrid_render_march_dcvgo) + shade kernels cover: the default HIP ops, fast_color_thres > 0, one
-        resolution for both grids, and either no rgbnet (3-channel k0, rgb = sigmoid(k0)) or the 3 x 128 rgbnet on
-        [k0 (12), view embedding] that ugrid_shade_supported(0, C, viewbase_pe) lists"""
-        if self._fused is False:
-            return False
-        s = self.s
-        if float(s['fast_color_thres']) <= 0 or tuple(s['density_grid'].shape[2:]) != tuple(s['k0_grid'].shape[2:]):
-            return False
-        C = int(s['k0_grid'].shape[1])
-        if len(s['rgbnet_weights']) == 0:
-            return C == 3
-        from . import _lib
-        from .fourier_render import rgbnet_fits_fused
-        w = s['rgbnet_weights']
-        return (rgbnet_fits_fused(w) and w[0].shape[1] == C + 3 + 6 * int(s['viewbase_pe'])
-                and bool(_lib.load().ugrid_shade_supported(0, C, int(s['viewbase_pe']))))
-
+    # -- fused inference path: BoundedRenderer.fused_supported as it stands (the march is ugrid_render_march_dcvgo, the rgbnet the
+    # 3 x 128 one on [k0 (12), view embedding]) ------------------------------------------------------------------
     frames_in_flight = 2      # run_render.render_viewpoints: 1080p frame 6.92 / 5.85 / 6.26 / 5.87 ms at 1 / 2 / 3 / 4 views in flight in the one sweep (the
                               # three-stream run probably had two streams on one hardware queue, profiles/r06/side_stream_queues.txt): nothing beyond two
 
-    def _fused_renderer(self):
-        """the fused march + shade renderer over this model's grids (built on first use)"""
-        if self._fused is None:
-            from .fourier_render import FourierGridRenderer
-            s = self.s
-            st = {'density_grid': s['density_grid'], 'k0_grid': s['k0_grid'], 'rgbnet_weights': s['rgbnet_weights'],
-                  'rgbnet_biases': s['rgbnet_biases'], 'scene_center': s['scene_center'], 'scene_radius': s['scene_radius'],
-                  'xyz_min': s['xyz_min'], 'xyz_max': s['xyz_max'], 'bg_len': s['bg_len'], 'fourier_freq_num': 0,
-                  'viewbase_pe': s['viewbase_pe'], 'act_shift': float(s['act_shift']), 'voxel_size_ratio': float(s['voxel_size_ratio']),
-                  'fast_color_thres': float(s['fast_color_thres']), 'contracted_norm': s['contracted_norm'], 'world_len': s['world_len'],
-                  'dcvgo': {'mask': s['mask'], 'xyz2ijk_scale': s['xyz2ijk_scale'], 'xyz2ijk_shift': s['xyz2ijk_shift']}}
-            self._fused = FourierGridRenderer(st, self.device)
-        return self._fused
-
-    def use_workspace_slot(self, k):
-        """Views in flight on two streams take a work list each (run_render.render_viewpoints, FourierGridRenderer.use_workspace_slot);
-        False: this model renders through the composed forward, one stream."""
-        if not self.fused_supported():
-            return False
-        self._fused_renderer().use_workspace_slot(k)
-        return True
-
-    @torch.no_grad()
-    def render_rays(self, rays_o, rays_d, viewdirs, **render_kwargs):
-        """Per-ray outputs of forward() -- rgb_marched, depth, alphainv_last, wsum_mid (what the render program consumes,
-        run_render.py:46) -- through the FUSED kernels: the whole chain of dcvgo.py:228-384 in two launches, no [N,S,3]
-        point tensor, no boolean compactions.  Falls back to forward() for models outside fused_supported().
-        render_kwargs as forward(): stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
-        if not self.fused_supported():
-            out = self.forward(rays_o, rays_d, viewdirs, **render_kwargs)
-            return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last', 'wsum_mid') if k in out}
-        fused = self._fused_renderer()
-        kw = dict(render_kwargs)
-        if 'bg' in kw and torch.is_tensor(kw['bg']):
-            kw['bg'] = kw['bg'].to(self.device)
-        out = fused(rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous(), **kw)
-        return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last', 'wsum_mid') if k in out}
+    def _fused_state(self):
+        s = self.s
+        st = self._bounded_state('dcvgo')
+        st.update({k: s[k] for k in ('scene_center', 'scene_radius', 'bg_len', 'contracted_norm', 'world_len')},
+                  act_shift=float(s['act_shift']))
+        return st
 
     def _t_table(self, stepsize):
         key = float(stepsize)
@@ -159,15 +95,6 @@ class DirectContractedVoxGORenderer:
             t, _ = sample_table(self.s['world_len'], key, self.s['bg_len'], t_boundary=2)     # dcvgo.py:243-250
             self._tables[key] = t.to(self.device)
         return self._tables[key]
-
-    def render_view(self, H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, **render_kwargs):
-        """One whole view through render_rays (fourier_render.render_view_of): {key: [H,W(,3)]} of the per-ray outputs."""
-        from .fourier_render import render_view_of
-        if not self.fused_supported():      # the composed forward takes no ray_order
-            rr = lambda o, d, v, ray_order=None, **kw: self.render_rays(o, d, v, **kw)
-        else:
-            rr = self.render_rays
-        return render_view_of(rr, self.device, H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, **render_kwargs)
 
     @torch.no_grad()
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
@@ -215,24 +142,8 @@ class DirectContractedVoxGORenderer:
             k = weights > thres
             pts, inner, tt, ray_id, step_id = pts[k], inner[k], tt[k], ray_id[k], step_id[k]
             density, alpha, weights = density[k], alpha[k], weights[k]
-        k0 = self.query(s['k0_grid'], pts, s['xyz_min'], s['xyz_max'], 0)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if len(s['rgbnet_weights']) == 0:
-            rgb = torch.sigmoid(k0)
-        else:
-            e = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            emb = torch.cat([viewdirs, e.sin(), e.cos()], -1)[ray_id]
-            h = torch.cat([k0, emb], -1)
-            n = len(s['rgbnet_weights'])
-            for i in range(n):
-                h = F.linear(h, s['rgbnet_weights'][i], s['rgbnet_biases'][i])
-                if i + 1 < n:
-                    h = torch.relu(h)
-            rgb = torch.sigmoid(h)
+        rgb, rgb_marched = self._colour(pts, ray_id, weights, alphainv_last, viewdirs, N, render_kwargs['bg'])
         dev = pts.device
-        rgb_marched = torch.zeros(N, 3, device=dev).index_add_(0, ray_id, weights.unsqueeze(-1) * rgb)
-        rgb_marched += alphainv_last.unsqueeze(-1) * render_kwargs['bg']
         wsum_mid = torch.zeros(N, device=dev).index_add_(0, ray_id[inner], weights[inner])
         sdist = 1 - 1 / (1 + tt)
         out = {'alphainv_last': alphainv_last, 'weights': weights, 'wsum_mid': wsum_mid, 'rgb_marched': rgb_marched,

@@ -14,7 +14,8 @@ implementation of the extension modules (the CPU oracle); the default is the HIP
 """
 import numpy as np
 import torch
-import torch.nn.functional as F
+
+from .bounded_render import BoundedRenderer
 
 
 def dvgo_state_from_params(xyz_min, xyz_max, num_voxels, num_voxels_base, alpha_init, density_grid, k0_grid, rgbnet_weights,
@@ -54,26 +55,15 @@ def dvgo_state_from_reference_checkpoint(ckpt):
     return st
 
 
-class DirectVoxGORenderer:
+class DirectVoxGORenderer(BoundedRenderer):
     """state: xyz_min/xyz_max [3], density_grid [1,1,X,Y,Z], k0_grid [1,C,X,Y,Z], rgbnet_weights/biases (lists),
     mask [mx,my,mz] bool, xyz2ijk_scale/shift [3], act_shift, voxel_size, voxel_size_ratio (0-d tensors or floats),
-    fast_color_thres, rgbnet_direct, viewbase_pe."""
+    fast_color_thres, rgbnet_direct, viewbase_pe.
 
-    def __init__(self, state, device, ops=None, query=None, grad_query=None):
-        dev = torch.device(device)
-        if ops is None:
-            if dev.type != "cuda":
-                raise RuntimeError("DirectVoxGORenderer needs a HIP device (no CPU path)")
-            from . import render_utils_cuda
-            from .grid import GridQuery, grid_query
-            self.ru, self.query, self.grad_query = render_utils_cuda, grid_query, GridQuery.apply
-        else:                                   # tests: another implementation of the extension modules
-            self.ru, self.query, self.grad_query = ops.render_utils_cuda, query, grad_query or query
-        self.device = dev
-        self.s = {k: (v.to(dev).contiguous() if torch.is_tensor(v) else
-                      ([x.to(dev).contiguous() for x in v] if isinstance(v, list) else v)) for k, v in state.items()}
-        self.viewfreq = torch.tensor([float(2 ** i) for i in range(int(state["viewbase_pe"]))], device=dev)
-        self._fused = None if ops is None else False      # fused render kernels: HIP library only, built on first use
+    render_rays: the whole chain of dvgo.py:306-425 in two launches.  The reference (and forward()) size the sample list by a
+    count kernel, a cumsum and a HOST READ of the total before the fill (render_utils_kernel.cu:100-260, `.item()` in
+    sample_pts_on_rays); in the fused march a lane marches its ray to the ray's own step count, so nothing is read back.
+    render_kwargs as forward(): near, stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
 
     @classmethod
     def from_reference_checkpoint(cls, ckpt, device):
@@ -81,83 +71,25 @@ class DirectVoxGORenderer:
         return cls(dvgo_state_from_reference_checkpoint(ckpt), device)
 
     # -- fused inference path ----------------------------------------------------------------------------------
+    @property
+    def rgbnet_residual(self):
+        """the diffuse + residual colour of dvgo.py:385-398: rgbnet on [k0[3:], embedding], k0[:3] added to its output"""
+        return len(self.s['rgbnet_weights']) > 0 and not bool(self.s['rgbnet_direct'])
+
     def fused_supported(self):
-        """the fused march (ugrid_render_march_dvgo) + shade kernels cover: the default HIP ops, fast_color_thres > 0, one
-        resolution for both grids, and either no rgbnet (3-channel k0, rgb = sigmoid(k0)) or the DIRECT 3 x 128 rgbnet on
-        [k0 (12), view embedding] that ugrid_shade_supported(0, C, viewbase_pe) lists -- rgbnet_direct, or the diffuse + residual
-        colour of dvgo.py:385-398 (rgbnet on [k0[3:], embedding], k0[:3] added to its output: the shade kernels' residual epilogue)"""
-        if self._fused is False:
-            return False
-        s = self.s
-        if float(s['fast_color_thres']) <= 0 or tuple(s['density_grid'].shape[2:]) != tuple(s['k0_grid'].shape[2:]):
-            return False
-        C = int(s['k0_grid'].shape[1])
-        if len(s['rgbnet_weights']) == 0:
-            return C == 3
-        from . import _lib
-        from .fourier_render import rgbnet_fits_fused
-        w = s['rgbnet_weights']
-        # rgbnet_direct: the network reads all C channels; else (dvgo.py:385-398) channels 3.. and the first three are added to
-        # its output -- the shade kernels' residual epilogue (include/ugrid_hip.h: UGRID_MLP_RESIDUAL), C >= 9
-        c_in = C if bool(s['rgbnet_direct']) else C - 3
-        return (rgbnet_fits_fused(w) and (bool(s['rgbnet_direct']) or C >= 9)
-                and w[0].shape[1] == c_in + 3 + 6 * int(s['viewbase_pe'])
-                and bool(_lib.load().ugrid_shade_supported(0, C, int(s['viewbase_pe']))))
+        """the fused march (ugrid_render_march_dvgo) + shade kernels cover what BoundedRenderer.fused_supported lists, the
+        rgbnet being the DIRECT 3 x 128 one on [k0 (12), view embedding] -- rgbnet_direct -- or the residual one: the network
+        reads channels 3.. and the first three are added to its output -- the shade kernels' residual epilogue
+        (include/ugrid_hip.h: UGRID_MLP_RESIDUAL), C >= 9"""
+        return super().fused_supported() and (not self.rgbnet_residual or int(self.s['k0_grid'].shape[1]) >= 9)
 
     frames_in_flight = 4      # run_render.render_viewpoints: a bounded scene's view (800 x 800 on the lego box: two launches of ~0.9 ms that leave most of
                               # the chip idle) gains from four views in flight -- 1.88 / 1.03 / 0.78 ms per view at 1 / 2 / 4 (profiles/r06/frames_in_flight_sweep.txt)
 
-    def _fused_renderer(self):
-        """the fused march + shade renderer over this model's grids (built on first use)"""
-        if self._fused is None:
-            from .fourier_render import FourierGridRenderer
-            s = self.s
-            lo, hi = s['xyz_min'], s['xyz_max']
-            st = {'density_grid': s['density_grid'], 'k0_grid': s['k0_grid'], 'rgbnet_weights': s['rgbnet_weights'],
-                  'rgbnet_biases': s['rgbnet_biases'], 'scene_center': (lo + hi) * 0.5, 'scene_radius': (hi - lo) * 0.5,
-                  'xyz_min': lo, 'xyz_max': hi, 'bg_len': 0.0, 'fourier_freq_num': 0, 'viewbase_pe': s['viewbase_pe'],
-                  'act_shift': float(s['act_shift']), 'voxel_size_ratio': float(s['voxel_size_ratio']),
-                  'fast_color_thres': float(s['fast_color_thres']), 'contracted_norm': 'inf', 'world_len': 0,
-                  'rgbnet_residual': (len(s['rgbnet_weights']) > 0 and not bool(s['rgbnet_direct'])),
-                  'dvgo': {'mask': s['mask'], 'xyz2ijk_scale': s['xyz2ijk_scale'], 'xyz2ijk_shift': s['xyz2ijk_shift'],
-                           'voxel_size': s['voxel_size']}}
-            self._fused = FourierGridRenderer(st, self.device)
-        return self._fused
-
-    def use_workspace_slot(self, k):
-        """Views in flight on two streams take a work list each (run_render.render_viewpoints, FourierGridRenderer.use_workspace_slot);
-        False: this model renders through the composed forward, one stream."""
-        if not self.fused_supported():
-            return False
-        self._fused_renderer().use_workspace_slot(k)
-        return True
-
-    @torch.no_grad()
-    def render_rays(self, rays_o, rays_d, viewdirs, **render_kwargs):
-        """Per-ray outputs of forward() -- rgb_marched, depth, alphainv_last (what the render program consumes,
-        run_render.py:46) -- through the FUSED kernels: the whole chain of dvgo.py:306-425 in two launches.  The reference
-        (and forward()) size the sample list by a count kernel, a cumsum and a HOST READ of the total before the fill
-        (render_utils_kernel.cu:100-260, `.item()` in sample_pts_on_rays); here a lane marches its ray to the ray's own
-        step count, so nothing is read back.  Falls back to forward() for models outside fused_supported().
-        render_kwargs as forward(): near, stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
-        if not self.fused_supported():
-            out = self.forward(rays_o, rays_d, viewdirs, **render_kwargs)
-            return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last') if k in out}
-        fused = self._fused_renderer()
-        kw = dict(render_kwargs)
-        if 'bg' in kw and torch.is_tensor(kw['bg']):
-            kw['bg'] = kw['bg'].to(self.device)
-        out = fused(rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous(), **kw)
-        return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last') if k in out}
-
-    def render_view(self, H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, **render_kwargs):
-        """One whole view through render_rays (fourier_render.render_view_of): {key: [H,W(,3)]} of the per-ray outputs."""
-        from .fourier_render import render_view_of
-        if not self.fused_supported():      # the composed forward takes no ray_order
-            rr = lambda o, d, v, ray_order=None, **kw: self.render_rays(o, d, v, **kw)
-        else:
-            rr = self.render_rays
-        return render_view_of(rr, self.device, H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, **render_kwargs)
+    def _fused_state(self):
+        st = self._bounded_state('dvgo', {'voxel_size': self.s['voxel_size']})
+        st.update(act_shift=float(self.s['act_shift']), rgbnet_residual=self.rgbnet_residual)
+        return st
 
     @torch.no_grad()
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
@@ -184,24 +116,7 @@ class DirectVoxGORenderer:
         if thres > 0:
             k = weights > thres
             weights, alpha, ray_pts, ray_id, step_id = weights[k], alpha[k], ray_pts[k], ray_id[k], step_id[k]
-        k0 = self.query(s['k0_grid'], ray_pts, s['xyz_min'], s['xyz_max'], 0)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if len(s['rgbnet_weights']) == 0:
-            rgb = torch.sigmoid(k0)
-        else:
-            e = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            emb = torch.cat([viewdirs, e.sin(), e.cos()], -1)[ray_id]
-            feat = torch.cat([k0 if s['rgbnet_direct'] else k0[:, 3:], emb], -1)
-            h = feat
-            n = len(s['rgbnet_weights'])
-            for i in range(n):
-                h = F.linear(h, s['rgbnet_weights'][i], s['rgbnet_biases'][i])
-                if i + 1 < n:
-                    h = torch.relu(h)
-            rgb = torch.sigmoid(h if s['rgbnet_direct'] else h + k0[:, :3])
-        rgb_marched = torch.zeros(N, 3, device=rays_o.device).index_add_(0, ray_id, weights.unsqueeze(-1) * rgb)
-        rgb_marched += alphainv_last.unsqueeze(-1) * render_kwargs['bg']
+        rgb, rgb_marched = self._colour(ray_pts, ray_id, weights, alphainv_last, viewdirs, N, render_kwargs['bg'])
         out = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched, 'raw_alpha': alpha,
                'raw_rgb': rgb, 'ray_id': ray_id}
         if render_kwargs.get('render_depth', False):

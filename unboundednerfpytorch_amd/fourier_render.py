@@ -106,6 +106,9 @@ class FourierGridRenderer:
     the same int((mpi_depth - 1) / stepsize) + 1 samples inside ugrid_render_march_mpi, the per-plane shift added to the density,
     interval = stepsize * voxel_size_ratio in double (a Python float product), `bg` honoured, depth = sum w * (step + 0.5) / n.
     mpi_render.DirectMPIGORenderer builds it.
+    At most one of the three: `self.variant` names it (None | 'dcvgo' | 'dvgo' | 'mpi') and `self.vp` is its record -- the mask
+    cache (mask, scale, shift), converted once, + voxel_size (dvgo) / act_shift (mpi); _variant_params fills the matching
+    ctypes struct (DcvgoParams / DvgoParams / MpiParams) per call.
     """
 
     def __init__(self, state, device, max_ws_bytes=48 << 30, pipeline=0, mlp_mode=None):
@@ -139,39 +142,26 @@ class FourierGridRenderer:
         self.voxel_size_ratio = float(state["voxel_size_ratio"])
         self.norm_l2 = {"inf": 0, "l2": 1}[state.get("contracted_norm", "inf")]
         self._vec = {k: [float(v) for v in state[k]] for k in ("scene_center", "scene_radius", "xyz_min", "xyz_max")}
-        self.dc = None
-        if state.get("dcvgo") is not None:
-            if self.F != 0:
-                raise RuntimeError("the DirectContractedVoxGO march is for single-level grids (fourier_freq_num = 0)")
-            d = state["dcvgo"]
-            self.dc = {"mask": d["mask"].to(dev).to(torch.bool).contiguous(),
-                       "scale": [float(x) for x in d["xyz2ijk_scale"]], "shift": [float(x) for x in d["xyz2ijk_shift"]]}
-            if self.dc["mask"].dim() != 3:
-                raise RuntimeError("dcvgo mask must be a [mx,my,mz] bool grid")
-        self.dv = None
-        if state.get("dvgo") is not None:
-            if self.F != 0 or self.dc is not None:
-                raise RuntimeError("the DirectVoxGO march is for single-level grids (fourier_freq_num = 0), without 'dcvgo'")
-            d = state["dvgo"]
-            self.dv = {"mask": d["mask"].to(dev).to(torch.bool).contiguous(), "voxel_size": d["voxel_size"],
-                       "scale": [float(x) for x in d["xyz2ijk_scale"]], "shift": [float(x) for x in d["xyz2ijk_shift"]]}
-            if self.dv["mask"].dim() != 3:
-                raise RuntimeError("dvgo mask must be a [mx,my,mz] bool grid")
-        self.mp = None
-        if state.get("mpi") is not None:
-            if self.F != 0 or self.dc is not None or self.dv is not None:
-                raise RuntimeError("the DirectMPIGO march is for single-level grids (fourier_freq_num = 0), without 'dcvgo' / 'dvgo'")
-            d = state["mpi"]
-            self.mp = {"mask": d["mask"].to(dev).to(torch.bool).contiguous(),
-                       "scale": [float(x) for x in d["xyz2ijk_scale"]], "shift": [float(x) for x in d["xyz2ijk_shift"]],
-                       "act_shift": torch.as_tensor(d["act_shift"]).to(dev, torch.float32).reshape(-1).contiguous()}
-            if self.mp["mask"].dim() != 3:
-                raise RuntimeError("mpi mask must be a [mx,my,mz] bool grid")
-            if self.mp["act_shift"].numel() != self.G[2] or not 2 <= self.G[2] <= 256:
-                raise RuntimeError("mpi act_shift must hold one value per plane of the grid's z axis (2..256 planes)")
-        if self.F == 0 and self.dc is None and self.dv is None and self.mp is None:
+        # march variant: None (FourierGrid) | "dcvgo" | "dvgo" | "mpi", and its record self.vp = the mask cache (mask, scale, shift)
+        # + what only that variant carries (dvgo: voxel_size; mpi: act_shift)
+        given = [n for n in ("dcvgo", "dvgo", "mpi") if state.get(n) is not None]
+        if given and (self.F != 0 or len(given) > 1):
+            raise RuntimeError("the DirectContractedVoxGO / DirectVoxGO / DirectMPIGO marches are for single-level grids "
+                               "(fourier_freq_num = 0), one of state['dcvgo'], state['dvgo'], state['mpi'] at a time")
+        if self.F == 0 and not given:
             raise RuntimeError("fourier_freq_num = 0 is the DirectContractedVoxGO / DirectVoxGO / DirectMPIGO path: pass "
                                "state['dcvgo'], state['dvgo'] or state['mpi']")
+        self.variant, self.vp = (given[0], dict(state[given[0]])) if given else (None, None)
+        if self.variant is not None:
+            v = self.vp
+            v["mask"] = v["mask"].to(dev).to(torch.bool).contiguous()
+            v["scale"], v["shift"] = [float(x) for x in v.pop("xyz2ijk_scale")], [float(x) for x in v.pop("xyz2ijk_shift")]
+            if v["mask"].dim() != 3:
+                raise RuntimeError("%s mask must be a [mx,my,mz] bool grid" % self.variant)
+            if self.variant == "mpi":
+                v["act_shift"] = torch.as_tensor(v["act_shift"]).to(dev, torch.float32).reshape(-1).contiguous()
+                if v["act_shift"].numel() != self.G[2] or not 2 <= self.G[2] <= 256:
+                    raise RuntimeError("mpi act_shift must hold one value per plane of the grid's z axis (2..256 planes)")
         if self.thres <= 0:
             raise RuntimeError("fast_color_thres must be > 0 (the reference forward is not usable at 0 either, "
                                "FourierGrid_model.py:600-614)")
@@ -228,7 +218,7 @@ class FourierGridRenderer:
     # -- helpers ---------------------------------------------------------------------------------
     def stepdist(self, stepsize):
         # python float * 0-d fp32 tensor -> fp32 product (dvgo.py:319)
-        return float(stepsize * torch.as_tensor(self.dv["voxel_size"], dtype=torch.float32))
+        return float(stepsize * torch.as_tensor(self.vp["voxel_size"], dtype=torch.float32))
 
     def mpi_steps(self, stepsize):
         """samples per ray of the DirectMPIGO march: int((mpi_depth - 1) / stepsize) + 1 (dmpigo.py:241)"""
@@ -236,23 +226,44 @@ class FourierGridRenderer:
 
     def tables(self, stepsize):
         key = float(stepsize)
-        if self.mp is not None:
+        if self.variant == "mpi":
             return None, None, self.mpi_steps(stepsize)
-        if self.dv is not None:
+        if self.variant == "dvgo":
             # no sample table: S = an upper bound of a ray's step count, ceil(box diagonal / stepdist) + 1 (sizes the work list)
             ext = [self._vec["xyz_max"][i] - self._vec["xyz_min"][i] for i in range(3)]
             diag = (ext[0] ** 2 + ext[1] ** 2 + ext[2] ** 2) ** 0.5
             return None, None, int(diag * (1 + 1e-5) / self.stepdist(stepsize)) + 2
         if key not in self._tables:
-            t, s = sample_table(self.world_len, key, self.bg_len, t_boundary=2 if self.dc is not None else 1.5)
+            t, s = sample_table(self.world_len, key, self.bg_len, t_boundary=2 if self.variant == "dcvgo" else 1.5)
             self._tables[key] = (t.to(self.device), s.to(self.device), int(t.numel()))
         return self._tables[key]
 
     def interval(self, stepsize):
-        if self.mp is not None:      # python float * python float (dmpigo.py:259), rounded to fp32 where Raw2Alpha takes it
+        if self.variant == "mpi":    # python float * python float (dmpigo.py:259), rounded to fp32 where Raw2Alpha takes it
             return float(stepsize * self.voxel_size_ratio)
         # python float * 0-d fp32 tensor -> fp32 product (FourierGrid_model.py:572)
         return float(torch.tensor(self.voxel_size_ratio, dtype=torch.float32) * stepsize)
+
+    def _variant_params(self, stepsize, S, render_kwargs):
+        """the march variant's ctypes struct (None for FourierGrid): the mask cache, filled in one place, + the variant's own fields"""
+        if self.variant is None:
+            return None
+        v = self.vp
+        q = {"dcvgo": _lib.DcvgoParams, "dvgo": _lib.DvgoParams, "mpi": _lib.MpiParams}[self.variant]()
+        q.mask = v["mask"].data_ptr()
+        q.mask_x, q.mask_y, q.mask_z = [int(x) for x in v["mask"].shape]
+        for i in range(3):
+            q.xyz2ijk_scale[i], q.xyz2ijk_shift[i] = v["scale"][i], v["shift"][i]
+        if self.variant == "dcvgo":
+            q.dist_thres = (2 + 2 * self.bg_len) / self.world_len * stepsize * 0.95      # dcvgo.py:285
+        elif self.variant == "dvgo":
+            q.near_clip, q.far_clip = float(render_kwargs["near"]), 1e9       # dvgo.py:318: the given far is ignored
+            q.stepdist = self.stepdist(stepsize)
+        else:
+            if float(render_kwargs.get("near", 0)) != 0 or float(render_kwargs.get("far", 1)) != 1:
+                raise ValueError("DirectMPIGO renders NDC rays with near = 0, far = 1 (dmpigo.py:237)")
+            q.mpi_depth, q.n_steps = self.G[2], S
+        return q
 
     def _params(self, n_rays, S, stepsize):
         p = _lib.RenderParams()
@@ -384,38 +395,12 @@ class FourierGridRenderer:
         rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
         depth = torch.empty(R, dtype=torch.float32, device=dev)
         last = torch.empty(R, dtype=torch.float32, device=dev)
-        wmid = torch.empty(R, dtype=torch.float32, device=dev) if self.dc is not None else None
-        dcp = None
-        if self.dc is not None:
-            dcp = _lib.DcvgoParams()
-            dcp.mask = self.dc["mask"].data_ptr()
-            dcp.mask_x, dcp.mask_y, dcp.mask_z = [int(x) for x in self.dc["mask"].shape]
-            for i in range(3):
-                dcp.xyz2ijk_scale[i], dcp.xyz2ijk_shift[i] = self.dc["scale"][i], self.dc["shift"][i]
-            dcp.dist_thres = (2 + 2 * self.bg_len) / self.world_len * stepsize * 0.95      # dcvgo.py:285
-        dvp = None
-        if self.dv is not None:
-            dvp = _lib.DvgoParams()
-            dvp.mask = self.dv["mask"].data_ptr()
-            dvp.mask_x, dvp.mask_y, dvp.mask_z = [int(x) for x in self.dv["mask"].shape]
-            for i in range(3):
-                dvp.xyz2ijk_scale[i], dvp.xyz2ijk_shift[i] = self.dv["scale"][i], self.dv["shift"][i]
-            dvp.near_clip, dvp.far_clip = float(render_kwargs["near"]), 1e9       # dvgo.py:318: the given far is ignored
-            dvp.stepdist = self.stepdist(stepsize)
-        mpp = None
-        if self.mp is not None:
-            if float(render_kwargs.get("near", 0)) != 0 or float(render_kwargs.get("far", 1)) != 1:
-                raise ValueError("DirectMPIGO renders NDC rays with near = 0, far = 1 (dmpigo.py:237)")
-            mpp = _lib.MpiParams()
-            mpp.mask = self.mp["mask"].data_ptr()
-            mpp.mask_x, mpp.mask_y, mpp.mask_z = [int(x) for x in self.mp["mask"].shape]
-            for i in range(3):
-                mpp.xyz2ijk_scale[i], mpp.xyz2ijk_shift[i] = self.mp["scale"][i], self.mp["shift"][i]
-            mpp.mpi_depth, mpp.n_steps = self.G[2], S
+        wmid = torch.empty(R, dtype=torch.float32, device=dev) if self.variant == "dcvgo" else None
+        vq = self._variant_params(stepsize, S, render_kwargs)
         timing = render_kwargs.get("timing")  # optional list collecting ([ev0, ev1, ev2], n_rays) per launch group
         with _lib.guard(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            if self.pipeline > 1 and R >= 64 * 64 * self.pipeline and self.dc is None and self.dv is None and self.mp is None:
+            if self.pipeline > 1 and R >= 64 * 64 * self.pipeline and self.variant is None:
                 self._forward_pipelined(rays_o, rays_d, viewdirs, t_tab, s_tab, S, stepsize, last, depth, rgb, timing)
             else:
                 chunk = self.rays_per_chunk(S)
@@ -428,16 +413,16 @@ class FourierGridRenderer:
                     if timing is not None:
                         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                         ev[0].record()
-                    if dcp is not None:
-                        _lib.check(_L.ugrid_render_march_dcvgo(p, ctypes.byref(dcp), _p(o_), _p(d_), _p(t_tab), _p(s_tab),
+                    if self.variant == "dcvgo":
+                        _lib.check(_L.ugrid_render_march_dcvgo(p, ctypes.byref(vq), _p(o_), _p(d_), _p(t_tab), _p(s_tab),
                                                                _p(self.density_bricks), _p(last[b:e]), _p(depth[b:e]), _p(wmid[b:e]),
                                                                _p(ws), st), "render_march_dcvgo")
-                    elif dvp is not None:
-                        _lib.check(_L.ugrid_render_march_dvgo(p, ctypes.byref(dvp), _p(o_), _p(d_), _p(self.density_bricks),
+                    elif self.variant == "dvgo":
+                        _lib.check(_L.ugrid_render_march_dvgo(p, ctypes.byref(vq), _p(o_), _p(d_), _p(self.density_bricks),
                                                               _p(last[b:e]), _p(depth[b:e]), _p(ws), st), "render_march_dvgo")
-                    elif mpp is not None:
-                        _lib.check(_L.ugrid_render_march_mpi(p, ctypes.byref(mpp), _p(o_), _p(d_), _p(self.density_bricks),
-                                                             _p(self.mp["act_shift"]), _p(last[b:e]), _p(depth[b:e]), _p(ws), st),
+                    elif self.variant == "mpi":
+                        _lib.check(_L.ugrid_render_march_mpi(p, ctypes.byref(vq), _p(o_), _p(d_), _p(self.density_bricks),
+                                                             _p(self.vp["act_shift"]), _p(last[b:e]), _p(depth[b:e]), _p(ws), st),
                                    "render_march_mpi")
                     else:
                         _lib.check(_L.ugrid_render_march(p, _p(o_), _p(d_), _p(t_tab), _p(s_tab), _p(self.density_bricks),
@@ -451,9 +436,9 @@ class FourierGridRenderer:
                         timing.append((ev, n))
                     self._last = ("split", n, S)
         out = {"alphainv_last": last, "rgb_marched": rgb, "n_max": S}
-        if self.dc is not None:
+        if wmid is not None:
             out["wsum_mid"] = wmid
-        if (self.dc is not None or self.dv is not None or self.mp is not None) and "bg" in render_kwargs:
+        if self.variant is not None and "bg" in render_kwargs:
             rgb += last.unsqueeze(-1) * render_kwargs["bg"]   # dcvgo.py:349-352 / dvgo.py:405 / dmpigo.py:314: rgb_marched += alphainv_last * bg
         if render_kwargs.get("render_depth", False):
             out["depth"] = depth

@@ -11,7 +11,8 @@ Two paths with the same outputs:
   render_rays  the fused march (ugrid_render_march_mpi) + shade kernels through FourierGridRenderer's `mpi` variant.
 """
 import torch
-import torch.nn.functional as F
+
+from .bounded_render import BoundedRenderer
 
 
 def mpi_state_from_params(xyz_min, xyz_max, num_voxels, mpi_depth, density_grid, act_shift_grid, k0_grid, rgbnet_weights,
@@ -49,27 +50,23 @@ def mpi_state_from_reference_checkpoint(ckpt):
     return st
 
 
-class DirectMPIGORenderer:
+class DirectMPIGORenderer(BoundedRenderer):
     """state: xyz_min/xyz_max [3] (the NDC box), density_grid [1,1,X,Y,D], act_shift [1,1,1,1,D], k0_grid [1,C,X,Y,D],
     rgbnet_weights/biases (lists; empty: rgb = sigmoid(k0), C = 3), mask [mx,my,mz] bool, xyz2ijk_scale/shift [3],
-    mpi_depth = D, voxel_size_ratio = 256 / D, fast_color_thres, viewbase_pe."""
+    mpi_depth = D, voxel_size_ratio = 256 / D, fast_color_thres, viewbase_pe.
+
+    render_rays: the whole chain of dmpigo.py:224-338 in two launches.  NDC rays (rays_o / rays_d from
+    get_rays_of_a_view(ndc=True)), world viewdirs; render_kwargs as forward(): near (0), far (1), stepsize, bg, render_depth,
+    plus FourierGridRenderer's ray_order."""
+
+    ndc = True
+    ray_order = "coherent"
+    # render_view: NDC rays generated on the device in 8 x 8 pixel blocks (fourier_render.render_view_of, ndc=True).  A view whose
+    # sides are not multiples of 8 (LLFF's 1008 x 756) is rendered in image order, which is coherent too: 64 consecutive pixels
+    # of a row.  (The "auto" check of FourierGridRenderer would sort such a list: NDC origins move across the image with the pixel.)
 
     def __init__(self, state, device, ops=None, query=None, mlp_mode=None):
-        dev = torch.device(device)
-        if ops is None:
-            if dev.type != "cuda":
-                raise RuntimeError("DirectMPIGORenderer needs a HIP device (no CPU path)")
-            from . import render_utils_cuda
-            from .grid import grid_query
-            self.ru, self.query = render_utils_cuda, grid_query
-        else:                                   # tests: another implementation of the extension modules
-            self.ru, self.query = ops.render_utils_cuda, query
-        self.device = dev
-        self.s = {k: (v.to(dev).contiguous() if torch.is_tensor(v) else
-                      ([x.to(dev).contiguous() for x in v] if isinstance(v, list) else v)) for k, v in state.items()}
-        self.viewfreq = torch.tensor([float(2 ** i) for i in range(int(state["viewbase_pe"]))], device=dev)
-        self.mlp_mode = mlp_mode
-        self._fused = None if ops is None else False      # fused render kernels: HIP library only, built on first use
+        super().__init__(state, device, ops, query, mlp_mode=mlp_mode)
 
     @classmethod
     def from_reference_checkpoint(cls, ckpt, device, **kw):
@@ -99,79 +96,18 @@ class DirectMPIGORenderer:
 
     # -- fused inference path ----------------------------------------------------------------------------------
     def fused_supported(self):
-        """the fused march (ugrid_render_march_mpi) + shade kernels cover: the default HIP ops, fast_color_thres > 0, one
-        resolution for both grids, mpi_depth <= 256, and either no rgbnet (3-channel k0) or a depth-3 rgbnet (width <= 128) on
-        [k0, view embedding] whose (0, C, viewbase_pe) ugrid_shade_supported lists -- (0, 9, 0) is configs/llff's net"""
-        if self._fused is False:
-            return False
+        """the fused march (ugrid_render_march_mpi) + shade kernels cover what BoundedRenderer.fused_supported lists -- (0, 9, 0)
+        is configs/llff's net -- with mpi_depth <= 256 (the march stages act_shift in LDS)"""
         s = self.s
-        if float(s['fast_color_thres']) <= 0 or tuple(s['density_grid'].shape[2:]) != tuple(s['k0_grid'].shape[2:]):
-            return False
-        if not 2 <= int(s['mpi_depth']) <= 256 or int(s['density_grid'].shape[4]) != int(s['mpi_depth']):
-            return False
-        C = int(s['k0_grid'].shape[1])
-        if len(s['rgbnet_weights']) == 0:
-            return C == 3
-        from . import _lib
-        from .fourier_render import rgbnet_fits_fused
-        w = s['rgbnet_weights']
-        return (rgbnet_fits_fused(w) and w[0].shape[1] == C + 3 + 6 * int(s['viewbase_pe'])
-                and bool(_lib.load().ugrid_shade_supported(0, C, int(s['viewbase_pe']))))
+        return (super().fused_supported() and 2 <= int(s['mpi_depth']) <= 256
+                and int(s['density_grid'].shape[4]) == int(s['mpi_depth']))
 
     frames_in_flight = 2      # run_render.render_viewpoints: views in flight on their own streams / work lists
 
-    def _fused_renderer(self):
-        """the fused march + shade renderer over this model's grids (built on first use)"""
-        if self._fused is None:
-            from .fourier_render import FourierGridRenderer
-            s = self.s
-            lo, hi = s['xyz_min'], s['xyz_max']
-            st = {'density_grid': s['density_grid'], 'k0_grid': s['k0_grid'], 'rgbnet_weights': s['rgbnet_weights'],
-                  'rgbnet_biases': s['rgbnet_biases'], 'scene_center': (lo + hi) * 0.5, 'scene_radius': (hi - lo) * 0.5,
-                  'xyz_min': lo, 'xyz_max': hi, 'bg_len': 0.0, 'fourier_freq_num': 0, 'viewbase_pe': s['viewbase_pe'],
-                  'act_shift': 0.0, 'voxel_size_ratio': float(s['voxel_size_ratio']),
-                  'fast_color_thres': float(s['fast_color_thres']), 'contracted_norm': 'inf', 'world_len': 0,
-                  'mpi': {'mask': s['mask'], 'xyz2ijk_scale': s['xyz2ijk_scale'], 'xyz2ijk_shift': s['xyz2ijk_shift'],
-                          'act_shift': s['act_shift'].reshape(-1)}}
-            self._fused = FourierGridRenderer(st, self.device, mlp_mode=self.mlp_mode)
-        return self._fused
-
-    def use_workspace_slot(self, k):
-        """Views in flight on several streams take a work list each (run_render.render_viewpoints); False: this model renders
-        through the composed forward, one stream."""
-        if not self.fused_supported():
-            return False
-        self._fused_renderer().use_workspace_slot(k)
-        return True
-
-    @torch.no_grad()
-    def render_rays(self, rays_o, rays_d, viewdirs, **render_kwargs):
-        """Per-ray outputs of forward() -- rgb_marched, depth, alphainv_last -- through the FUSED kernels: the whole chain of
-        dmpigo.py:224-338 in two launches, no boolean-mask compactions, no host syncs.  NDC rays (rays_o / rays_d from
-        get_rays_of_a_view(ndc=True)), world viewdirs.  Falls back to forward() for models outside fused_supported().
-        render_kwargs as forward(): near (0), far (1), stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
-        if not self.fused_supported():
-            out = self.forward(rays_o, rays_d, viewdirs, **render_kwargs)
-            return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last') if k in out}
-        fused = self._fused_renderer()
-        kw = dict(render_kwargs)
-        if 'bg' in kw and torch.is_tensor(kw['bg']):
-            kw['bg'] = kw['bg'].to(self.device)
-        out = fused(rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous(), **kw)
-        return {k: out[k] for k in ('rgb_marched', 'depth', 'alphainv_last') if k in out}
-
-    def render_view(self, H, W, K, c2w, inverse_y=False, flip_x=False, flip_y=False, **render_kwargs):
-        """One whole view through render_rays: NDC rays generated on the device in 8 x 8 pixel blocks
-        (fourier_render.render_view_of, ndc=True); {key: [H,W(,3)]} of the per-ray outputs.  A view whose sides are not
-        multiples of 8 (LLFF's 1008 x 756) is rendered in image order, which is coherent too: 64 consecutive pixels of a row.
-        (The "auto" check of FourierGridRenderer would sort such a list: NDC origins move across the image with the pixel.)"""
-        from .fourier_render import render_view_of
-        if not self.fused_supported():      # the composed forward takes no ray_order
-            rr = lambda o, d, v, ray_order=None, **kw: self.render_rays(o, d, v, **kw)
-        else:
-            rr = lambda o, d, v, ray_order="coherent", **kw: self.render_rays(o, d, v, ray_order=ray_order, **kw)
-        return render_view_of(rr, self.device, H, W, K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, ndc=True,
-                              **render_kwargs)
+    def _fused_state(self):
+        st = self._bounded_state('mpi', {'act_shift': self.s['act_shift'].reshape(-1)})
+        st['act_shift'] = 0.0          # the per-plane shift is part of the density; Raw2Alpha gets 0 (dmpigo.py:222,275)
+        return st
 
     @torch.no_grad()
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
@@ -201,23 +137,7 @@ class DirectMPIGORenderer:
         if thres > 0:
             k = weights > thres
             weights, alpha, ray_pts, ray_id, step_id = weights[k], alpha[k], ray_pts[k], ray_id[k], step_id[k]
-        k0 = self.query(s['k0_grid'], ray_pts, s['xyz_min'], s['xyz_max'], 0)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if len(s['rgbnet_weights']) == 0:
-            rgb = torch.sigmoid(k0)
-        else:
-            e = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            emb = torch.cat([viewdirs, e.sin(), e.cos()], -1)[ray_id]
-            h = torch.cat([k0, emb], -1)
-            n = len(s['rgbnet_weights'])
-            for i in range(n):
-                h = F.linear(h, s['rgbnet_weights'][i], s['rgbnet_biases'][i])
-                if i + 1 < n:
-                    h = torch.relu(h)
-            rgb = torch.sigmoid(h)
-        rgb_marched = torch.zeros(N, 3, device=dev).index_add_(0, ray_id, weights.unsqueeze(-1) * rgb)
-        rgb_marched += alphainv_last.unsqueeze(-1) * render_kwargs['bg']
+        rgb, rgb_marched = self._colour(ray_pts, ray_id, weights, alphainv_last, viewdirs, N, render_kwargs['bg'])
         sv = (step_id + 0.5) / n_samples
         out = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched, 'raw_alpha': alpha,
                'raw_rgb': rgb, 'ray_id': ray_id, 'n_max': n_samples, 's': sv}
