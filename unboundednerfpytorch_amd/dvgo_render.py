@@ -8,11 +8,10 @@ The compaction steps (boolean masks) and the tiny rgbnet use torch on the device
 reference does; every kernel the reference has natively is the HIP one.
 
 Also the training-ray preparation that leans on the same kernels: `hit_coarse_geo`
-(dvgo.py:292-304), `voxel_count_views` (dvgo.py:247-277) and `get_training_rays_in_maskcache_sampling`
+(dvgo.py:292-304) and `voxel_count_views` (dvgo.py:247-277), both one-line calls of train_rays' functions of those names, and `get_training_rays_in_maskcache_sampling`
 (dvgo.py:619-657).  `ops` / `query` / `grad_query` exist for tests: they let the same composition run against another
 implementation of the extension modules (the CPU oracle); the default is the HIP library, which needs a GPU.
 """
-import numpy as np
 import torch
 
 from .bounded_render import BoundedRenderer
@@ -126,53 +125,19 @@ class DirectVoxGORenderer(BoundedRenderer):
     __call__ = forward
 
     # -- training-ray preparation ---------------------------------------------------------------------------
-    @torch.no_grad()
     def hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         """bool [...]: does the ray pass through a cell the mask cache marks as possibly occupied? (dvgo.py:292-304)"""
+        from .train_rays import hit_coarse_geo
         s = self.s
-        far = 1e9
-        shape = rays_o.shape[:-1]
-        o = rays_o.reshape(-1, 3).contiguous()
-        d = rays_d.reshape(-1, 3).contiguous()
-        ray_pts, mask_outbbox, ray_id = self.ru.sample_pts_on_rays(o, d, s['xyz_min'], s['xyz_max'], near, far,
-                                                                  stepsize * s['voxel_size'])[:3]
-        inb = ~mask_outbbox
-        pts_in, rid_in = ray_pts[inb], ray_id[inb]
-        occ = self.ru.maskcache_lookup(s['mask'], pts_in.contiguous(), s['xyz2ijk_scale'], s['xyz2ijk_shift'])
-        hit = torch.zeros(o.shape[0], dtype=torch.bool, device=o.device)
-        hit[rid_in[occ]] = True
-        return hit.reshape(shape)
+        return hit_coarse_geo(self.ru, rays_o, rays_d, s['xyz_min'], s['xyz_max'], near, stepsize * s['voxel_size'], s['mask'],
+                              s['xyz2ijk_scale'], s['xyz2ijk_shift'])
 
     def voxel_count_views(self, rays_o_tr, rays_d_tr, imsz, near, far, stepsize, downrate=1, irregular_shape=False):
-        """Per-voxel count of the training views that see it (dvgo.py:247-277): for every image the trilinear
-        footprint of its rays' samples is scattered into a zero grid -- here by the lookup's scatter backward -- and a
-        voxel counts as seen when its accumulated weight exceeds 1."""
+        """Per-voxel count of the training views that see it (dvgo.py:247-277), scattered by self.grad_query's backward"""
+        from .train_rays import voxel_count_views
         s = self.s
-        far = 1e9
-        ws = s['world_size']
-        dev = s['density_grid'].device
-        n_samples = int(np.linalg.norm(ws.cpu().numpy().astype(np.float64) + 1) / stepsize) + 1
-        rng = torch.arange(n_samples, device=dev)[None].float()
-        count = torch.zeros_like(s['density_grid'])
-        for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
-            ones = torch.zeros_like(s['density_grid']).requires_grad_(True)
-            if irregular_shape:
-                o_chunks, d_chunks = o_img.split(10000), d_img.split(10000)
-            else:
-                o_chunks = o_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
-                d_chunks = d_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
-            for o, d in zip(o_chunks, d_chunks):
-                vec = torch.where(d == 0, torch.full_like(d, 1e-6), d)
-                rate_a = (s['xyz_max'] - o) / vec
-                rate_b = (s['xyz_min'] - o) / vec
-                t_min = torch.minimum(rate_a, rate_b).amax(-1).clamp(min=near, max=far)
-                step = stepsize * s['voxel_size'] * rng
-                interpx = t_min[..., None] + step / d.norm(dim=-1, keepdim=True)
-                pts = o[..., None, :] + d[..., None, :] * interpx[..., None]
-                self.grad_query(ones, pts, s['xyz_min'], s['xyz_max'], 0).sum().backward()
-            with torch.no_grad():
-                count += (ones.grad > 1)
-        return count
+        return voxel_count_views(self.grad_query, s['xyz_min'], s['xyz_max'], s['voxel_size'], s['world_size'], s['density_grid'].shape,
+                                 rays_o_tr, rays_d_tr, imsz, near, stepsize, downrate, irregular_shape)
 
 
 @torch.no_grad()

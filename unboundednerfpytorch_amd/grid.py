@@ -4,7 +4,11 @@
                  (replaces F.grid_sample and its atomics-bound backward in training)
   FourierGrid    drop-in for the reference's nn.Module of that name (FourierGrid_grid.py:43-103): same constructor,
                  parameter / buffer names (state_dict compatible) and methods
-  MaskGrid       <- MaskGrid.forward (grid.py:230-239, FourierGrid_grid.py:159-168)"""
+  MaskGrid       <- MaskGrid.forward (grid.py:230-239, FourierGrid_grid.py:159-168)
+  TrainMarch / TrainSample / TrainSampleVox
+                 the fused sampling of the training forwards as autograd ops.  The two sample ops differ in their input checks
+                 and their march entry point only: what follows the march (_sample_stages) and the backward are one piece of
+                 code, and every op -- native_step.VoxGOStep included -- takes its per-(ray, slot) scratch from scratch()"""
 import torch
 import torch.nn.functional as F
 
@@ -78,6 +82,22 @@ class GridQuery(torch.autograd.Function):
         return grad_grid, None, None, None, None
 
 
+_scratch = {}      # width -> ((device, n), arrays)
+
+
+def scratch(dev, n, width=5):
+    """The march kernels' per-(ray, slot) scratch, kept between steps: points [n,3], density [n], step [n] i32 and, for the
+    sample ops (width 5: TrainSample, TrainSampleVox, native_step.VoxGOStep), weight [n] and transmittance [n].  Written by
+    the march and read by the compaction of the SAME forward (no backward takes it), so the ops share it; one ray-batch shape
+    at a time per width: 8 + 4 * width bytes per (ray, slot)."""
+    if _scratch.get(width, (None,))[0] != (dev, n):
+        _scratch.pop(width, None)          # the old shape's arrays go before the new ones come
+        _scratch[width] = ((dev, n), (torch.empty(n, 3, device=dev), torch.empty(n, device=dev),
+                                      torch.empty(n, dtype=torch.int32, device=dev))
+                           + tuple(torch.empty(n, device=dev) for _ in range(width - 3)))
+    return _scratch[width][1]
+
+
 class TrainMarch(torch.autograd.Function):
     """Fused stage 1 of the training forward (FourierGrid_model.py:554-598): rays -> the samples whose alpha exceeds
     fast_color_thres, compacted ray-major, with their raw densities -- sample_ray, the density lookup of all R*S points,
@@ -88,7 +108,6 @@ class TrainMarch(torch.autograd.Function):
     forward(grid [P,1,X,Y,Z], rays_o [R,3], rays_d [R,3], t [S], scene_center, scene_radius, xyz_min, xyz_max, bg_len,
             norm_l2, act_shift, interval, thres, freq_num) -> pts [M1,3], density [M1], ray_id [M1] i64, step_id [M1] i64,
             t [M1]"""
-    _scratch = {}
 
     @staticmethod
     def forward(ctx, grid, rays_o, rays_d, t, scene_center, scene_radius, xyz_min, xyz_max, bg_len, norm_l2, act_shift,
@@ -102,12 +121,7 @@ class TrainMarch(torch.autograd.Function):
         P, _, X, Y, Z = grid.shape
         R, S = rays_o.shape[0], t.numel()
         dev = grid.device
-        key = (dev, R * S)
-        sc = TrainMarch._scratch.get(key)
-        if sc is None:
-            TrainMarch._scratch.clear()          # one ray-batch shape at a time: 24 B per (ray, sample)
-            sc = (torch.empty(R * S, 3, device=dev), torch.empty(R * S, device=dev), torch.empty(R * S, dtype=torch.int32, device=dev))
-            TrainMarch._scratch[key] = sc
+        sc = scratch(dev, R * S, width=3)
         count = torch.empty(R, dtype=torch.int32, device=dev)
         c3 = (ctypes.c_float * 3)(*[float(x) for x in scene_center])
         r3 = (ctypes.c_float * 3)(*[float(x) for x in scene_radius])
@@ -156,11 +170,10 @@ class TrainMarch(torch.autograd.Function):
 class TrainSample(torch.autograd.Function):
     """Stages 1 and 2 of the training forward's sampling (FourierGrid_model.py:554-629) as ONE op: TrainMarch, Raw2Alpha,
     Alphas2Weights, the weight mask and its gathers -- include/ugrid_hip.h: ugrid_train_sample / _compact / _backward.  One
-    march kernel (a ray ends where its transmittance does), one cumsum + ONE host read (M1, M2), one compaction; the backward
-    is one pass over the stage-1 samples + the density lookup's scatter.  Returns the stage-2 samples
-    (pts, raw density, alpha, weights, ray_id, step_id, t) and alphainv_last [R]; differentiable in the density grid through
-    `weights`, `alphainv_last` and the raw `density` output."""
-    _scratch = {}
+    march kernel (a ray ends where its transmittance does), one cumsum + ONE host read (M1, M2), one compaction
+    (_sample_stages); the backward is one pass over the stage-1 samples + the density lookup's scatter.  Returns the stage-2
+    samples (pts, raw density, alpha, weights, ray_id, step_id, t) and alphainv_last [R]; differentiable in the density grid
+    through `weights`, `alphainv_last` and the raw `density` output."""
 
     @staticmethod
     def forward(ctx, grid, rays_o, rays_d, t, scene_center, scene_radius, xyz_min, xyz_max, bg_len, norm_l2, act_shift,
@@ -173,49 +186,20 @@ class TrainSample(torch.autograd.Function):
             raise RuntimeError("density grid must be [P,1,X,Y,Z]")
         P, _, X, Y, Z = grid.shape
         R, S = rays_o.shape[0], t.numel()
-        dev = grid.device
-        key = (dev, R * S)
-        sc = TrainSample._scratch.get(key)
-        if sc is None:
-            TrainSample._scratch.clear()          # one ray-batch shape at a time: 32 B per (ray, sample)
-            sc = (torch.empty(R * S, 3, device=dev), torch.empty(R * S, device=dev), torch.empty(R * S, dtype=torch.int32, device=dev),
-                  torch.empty(R * S, device=dev), torch.empty(R * S, device=dev))
-            TrainSample._scratch[key] = sc
-        counts = torch.empty(2, R, dtype=torch.int32, device=dev)
-        ainv = torch.empty(R, device=dev)
         c3 = (ctypes.c_float * 3)(*[float(x) for x in scene_center])
         r3 = (ctypes.c_float * 3)(*[float(x) for x in scene_radius])
         F_ = max(int(freq_num), 0)
-        with _lib.guard(dev):
-            st = _lib.stream_of(grid)
+        consts = (float(act_shift), float(interval), float(thres))
+
+        def march(*outs):
             _lib.check(_L.ugrid_train_sample(_lib.ptr(grid), P, X, Y, Z, F_, _lib.ptr(rays_o), _lib.ptr(rays_d), R, _lib.ptr(t), S,
                                              ctypes.cast(c3, ctypes.c_void_p), ctypes.cast(r3, ctypes.c_void_p), _lib.ptr(xyz_min),
-                                             _lib.ptr(xyz_max), float(bg_len), int(bool(norm_l2)), float(act_shift), float(interval),
-                                             float(thres), *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(counts[1]),
-                                             _lib.ptr(ainv), st), "train_sample")
-            off = torch.cumsum(counts, 1, dtype=torch.int64)            # [2,R] inclusive
-            M1, M2 = (int(x) for x in off[:, -1].tolist()) if R > 0 else (0, 0)     # the one host read
-            pts1, dens1, w1, T1 = torch.empty(M1, 3, device=dev), torch.empty(M1, device=dev), torch.empty(M1, device=dev), \
-                torch.empty(M1, device=dev)
-            pos2 = torch.empty(M1, dtype=torch.int32, device=dev)
-            pts2, dens2, alpha2, w2, tt2 = torch.empty(M2, 3, device=dev), torch.empty(M2, device=dev), torch.empty(M2, device=dev), \
-                torch.empty(M2, device=dev), torch.empty(M2, device=dev)
-            ray2, step2 = torch.empty(M2, dtype=torch.int64, device=dev), torch.empty(M2, dtype=torch.int64, device=dev)
-            if M1 > 0:
-                _lib.check(_L.ugrid_train_sample_compact(
-                    R, S, float(act_shift), float(interval), float(thres), *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]),
-                    _lib.ptr(off[0]), _lib.ptr(counts[1]), _lib.ptr(off[1]), _lib.ptr(t), _lib.ptr(pts1), _lib.ptr(dens1), _lib.ptr(w1),
-                    _lib.ptr(T1), _lib.ptr(pos2), _lib.ptr(pts2), _lib.ptr(dens2), _lib.ptr(alpha2), _lib.ptr(w2), _lib.ptr(ray2),
-                    _lib.ptr(step2), _lib.ptr(tt2), st), "train_sample_compact")
-        ctx.save_for_backward(pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max)
-        ctx.shape, ctx.freq_num, ctx.consts = tuple(grid.shape), F_, (float(act_shift), float(interval))
-        ctx.pool_key, ctx.grid_stride = _gradpool.key_of(grid), tuple(grid.stride())
-        ctx.mark_non_differentiable(pts2, alpha2, ray2, step2, tt2)
-        return pts2, dens2, alpha2, w2, ainv, ray2, step2, tt2
+                                             _lib.ptr(xyz_max), float(bg_len), int(bool(norm_l2)), *consts, *outs), "train_sample")
+        return _sample_stages(ctx, grid, R, S, t, xyz_min, xyz_max, consts, F_, march, vox=False)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_pts, g_dens2, g_alpha, g_w2, g_ainv, g_ray, g_step, g_t):
+    def backward(ctx, g_pts, g_dens2, g_alpha, g_w2, g_ainv, *g_rest):
         pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max = ctx.saved_tensors
         P, C, X, Y, Z = ctx.shape
         dev = pts1.device
@@ -235,22 +219,21 @@ class TrainSample(torch.autograd.Function):
                            "train_sample_backward")
                 _lib.check(_L.ugrid_grid_query_backward(_lib.ptr(g1), P, C, X, Y, Z, _lib.ptr(pts1), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
                                                         ctx.freq_num, M1, _lib.ptr(grad_grid), st), "grid_query_backward")
-        return (grad_grid,) + (None,) * 13
+        return (grad_grid,) + (None,) * (len(ctx.needs_input_grad) - 1)      # (this forward's inputs or TrainSampleVox's)
 
 
-class TrainSampleVox(torch.autograd.Function):
+class TrainSampleVox(TrainSample):
     """TrainSample for the reference's two dense-grid models: the sampling of DirectContractedVoxGO.forward (dcvgo.py:228-330,
     cfg['mode'] == 'dcvgo') and of DirectVoxGO.forward (dvgo.py:306-375, 'dvgo') as one march + one compaction
     (include/ugrid_hip.h: ugrid_train_sample_dcvgo / _dvgo / _compact_vox), differentiable in the density grid through
-    `weights`, `alphainv_last` and the raw `density` output -- the backward is TrainSample's (ugrid_train_sample_backward +
-    the lookup's scatter).
+    `weights`, `alphainv_last` and the raw `density` output -- the backward is TrainSample's, inherited (ugrid_train_sample_backward
+    + the lookup's scatter).
 
     forward(grid [1,1,X,Y,Z], rays_o [R,3], rays_d [R,3], t [S] or None, xyz_min, xyz_max, mask [mi,mj,mk] bool, cfg) ->
         pts [M2,3], density [M2], alpha [M2], weights [M2], alphainv_last [R], ray_id [M2] i64, step_id [M2] i64, t [M2]
         (dvgo: float(step_id)), inner [M2] bool (dvgo: all True)
     cfg (host values): mode, act_shift, interval, thres, mask_scale[3], mask_shift[3] and
         dcvgo: scene_center[3], scene_radius[3], bg_len, norm_l2, dist_thres;   dvgo: near, far, stepdist, slots"""
-    _scratch = {}
 
     @staticmethod
     def forward(ctx, grid, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg):
@@ -273,80 +256,65 @@ class TrainSampleVox(torch.autograd.Function):
             S = int(cfg['slots'])
         else:
             raise ValueError(mode)
-        dev = grid.device
-        key = (dev, R * S)
-        sc = TrainSampleVox._scratch.get(key)
-        if sc is None:
-            TrainSampleVox._scratch.clear()          # one ray-batch shape at a time: 32 B per (ray, slot)
-            sc = (torch.empty(R * S, 3, device=dev), torch.empty(R * S, device=dev), torch.empty(R * S, dtype=torch.int32, device=dev),
-                  torch.empty(R * S, device=dev), torch.empty(R * S, device=dev))
-            TrainSampleVox._scratch[key] = sc
-        counts = torch.empty(2, R, dtype=torch.int32, device=dev)
-        ainv = torch.empty(R, device=dev)
         f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
         md = (ctypes.c_int32 * 3)(*[int(x) for x in mask.shape])
         ms, mh = f3(cfg['mask_scale']), f3(cfg['mask_shift'])
         vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        shift, interval, thres = float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres'])
-        with _lib.guard(dev):
-            st = _lib.stream_of(grid)
-            if mode == 'dcvgo':
-                c3, r3 = f3(cfg['scene_center']), f3(cfg['scene_radius'])
+        consts = (float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres']))
+        if mode == 'dcvgo':
+            c3, r3 = f3(cfg['scene_center']), f3(cfg['scene_radius'])
+
+            def march(*outs):
                 _lib.check(_L.ugrid_train_sample_dcvgo(
                     _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, _lib.ptr(t), S, vp(c3), vp(r3), _lib.ptr(xyz_min),
                     _lib.ptr(xyz_max), float(cfg['bg_len']), int(bool(cfg['norm_l2'])), float(cfg['dist_thres']), _lib.ptr(mask), vp(md),
-                    vp(ms), vp(mh), shift, interval, thres, *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(counts[1]),
-                    _lib.ptr(ainv), st), "train_sample_dcvgo")
-            else:
+                    vp(ms), vp(mh), *consts, *outs), "train_sample_dcvgo")
+        else:
+            def march(*outs):
                 _lib.check(_L.ugrid_train_sample_dvgo(
                     _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-                    float(cfg['near']), float(cfg['far']), float(cfg['stepdist']), _lib.ptr(mask), vp(md), vp(ms), vp(mh), shift,
-                    interval, thres, *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(counts[1]), _lib.ptr(ainv), st),
-                    "train_sample_dvgo")
-            off = torch.cumsum(counts, 1, dtype=torch.int64)            # [2,R] inclusive
-            M1, M2 = (int(x) for x in off[:, -1].tolist()) if R > 0 else (0, 0)     # the one host read
-            pts1, dens1, w1, T1 = torch.empty(M1, 3, device=dev), torch.empty(M1, device=dev), torch.empty(M1, device=dev), \
-                torch.empty(M1, device=dev)
-            pos2 = torch.empty(M1, dtype=torch.int32, device=dev)
-            pts2, dens2, alpha2, w2, tt2 = torch.empty(M2, 3, device=dev), torch.empty(M2, device=dev), torch.empty(M2, device=dev), \
-                torch.empty(M2, device=dev), torch.empty(M2, device=dev)
-            ray2, step2 = torch.empty(M2, dtype=torch.int64, device=dev), torch.empty(M2, dtype=torch.int64, device=dev)
-            inner2 = torch.ones(M2, dtype=torch.bool, device=dev)
-            if M1 > 0:
-                _lib.check(_L.ugrid_train_sample_compact_vox(
-                    R, S, shift, interval, thres, *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(off[0]), _lib.ptr(counts[1]),
-                    _lib.ptr(off[1]), _lib.ptr(t) if mode == 'dcvgo' else None, _lib.ptr(pts1), _lib.ptr(dens1), _lib.ptr(w1),
-                    _lib.ptr(T1), _lib.ptr(pos2), _lib.ptr(pts2), _lib.ptr(dens2), _lib.ptr(alpha2), _lib.ptr(w2), _lib.ptr(ray2),
-                    _lib.ptr(step2), _lib.ptr(tt2), _lib.ptr(inner2) if mode == 'dcvgo' else None, st), "train_sample_compact_vox")
-        ctx.save_for_backward(pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max)
-        ctx.shape, ctx.consts = tuple(grid.shape), (shift, interval)
-        ctx.pool_key, ctx.grid_stride = _gradpool.key_of(grid), tuple(grid.stride())
-        ctx.mark_non_differentiable(pts2, alpha2, ray2, step2, tt2, inner2)
-        return pts2, dens2, alpha2, w2, ainv, ray2, step2, tt2, inner2
+                    float(cfg['near']), float(cfg['far']), float(cfg['stepdist']), _lib.ptr(mask), vp(md), vp(ms), vp(mh), *consts,
+                    *outs), "train_sample_dvgo")
+        return _sample_stages(ctx, grid, R, S, t if mode == 'dcvgo' else None, xyz_min, xyz_max, consts, 0, march, vox=True)
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_pts, g_dens2, g_alpha, g_w2, g_ainv, g_ray, g_step, g_t, g_inner):
-        pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max = ctx.saved_tensors
-        P, C, X, Y, Z = ctx.shape
-        dev = pts1.device
-        grad_grid = _gradpool.take(ctx.pool_key, ctx.shape, ctx.grid_stride, dev)
-        if grad_grid is None:
-            grad_grid = torch.zeros(ctx.shape, dtype=torch.float32, device=dev)
-        M1, R = pts1.shape[0], ainv.shape[0]
+
+def _sample_stages(ctx, grid, R, S, t, xyz_min, xyz_max, consts, freq_num, march, vox):
+    """What TrainSample and TrainSampleVox do after their input checks: the scratch, `march(*pointers of the scratch, the two
+    per-ray counts and alphainv_last, stream)` -- the caller's march entry point --, the cumsum and the ONE host read (M1, M2),
+    the stage-1 / stage-2 arrays, the compaction (`vox`: ugrid_train_sample_compact_vox, which also writes the inner flags of
+    the samples when there is a sample table `t`), and what the shared backward reads from ctx."""
+    dev = grid.device
+    sc = scratch(dev, R * S)
+    counts = torch.empty(2, R, dtype=torch.int32, device=dev)
+    ainv = torch.empty(R, device=dev)
+    shift, interval, thres = consts
+    with _lib.guard(dev):
+        st = _lib.stream_of(grid)
+        march(*[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(counts[1]), _lib.ptr(ainv), st)
+        off = torch.cumsum(counts, 1, dtype=torch.int64)            # [2,R] inclusive
+        M1, M2 = (int(x) for x in off[:, -1].tolist()) if R > 0 else (0, 0)     # the one host read
+        pts1, dens1, w1, T1 = torch.empty(M1, 3, device=dev), torch.empty(M1, device=dev), torch.empty(M1, device=dev), \
+            torch.empty(M1, device=dev)
+        pos2 = torch.empty(M1, dtype=torch.int32, device=dev)
+        pts2, dens2, alpha2, w2, tt2 = torch.empty(M2, 3, device=dev), torch.empty(M2, device=dev), torch.empty(M2, device=dev), \
+            torch.empty(M2, device=dev), torch.empty(M2, device=dev)
+        ray2, step2 = torch.empty(M2, dtype=torch.int64, device=dev), torch.empty(M2, dtype=torch.int64, device=dev)
+        inner2 = (torch.ones(M2, dtype=torch.bool, device=dev),) if vox else ()
         if M1 > 0:
-            f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
-            g_dens2, g_w2, g_ainv = f32(g_dens2), f32(g_w2), f32(g_ainv)
-            g1 = torch.empty(M1, 1, device=dev)
-            with _lib.guard(dev):
-                st = _lib.stream_of(pts1)
-                _lib.check(_L.ugrid_train_sample_backward(R, ctx.consts[0], ctx.consts[1], _lib.ptr(dens1), _lib.ptr(w1), _lib.ptr(T1),
-                                                          _lib.ptr(pos2), _lib.ptr(counts[0]), _lib.ptr(off[0]), _lib.ptr(ainv),
-                                                          _lib.ptr(g_w2), _lib.ptr(g_ainv), _lib.ptr(g_dens2), _lib.ptr(g1), st),
-                           "train_sample_backward")
-                _lib.check(_L.ugrid_grid_query_backward(_lib.ptr(g1), P, C, X, Y, Z, _lib.ptr(pts1), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-                                                        0, M1, _lib.ptr(grad_grid), st), "grid_query_backward")
-        return (grad_grid,) + (None,) * 7
+            tp = _lib.ptr(t) if t is not None else None
+            args = (R, S, shift, interval, thres, *[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(off[0]), _lib.ptr(counts[1]),
+                    _lib.ptr(off[1]), tp, _lib.ptr(pts1), _lib.ptr(dens1), _lib.ptr(w1), _lib.ptr(T1), _lib.ptr(pos2), _lib.ptr(pts2),
+                    _lib.ptr(dens2), _lib.ptr(alpha2), _lib.ptr(w2), _lib.ptr(ray2), _lib.ptr(step2), _lib.ptr(tt2))
+            if vox:
+                _lib.check(_L.ugrid_train_sample_compact_vox(*args, _lib.ptr(inner2[0]) if t is not None else None, st),
+                           "train_sample_compact_vox")
+            else:
+                _lib.check(_L.ugrid_train_sample_compact(*args, st), "train_sample_compact")
+    ctx.save_for_backward(pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max)
+    ctx.shape, ctx.freq_num, ctx.consts = tuple(grid.shape), freq_num, (shift, interval)
+    ctx.pool_key, ctx.grid_stride = _gradpool.key_of(grid), tuple(grid.stride())
+    ctx.mark_non_differentiable(pts2, alpha2, ray2, step2, tt2, *inner2)
+    return (pts2, dens2, alpha2, w2, ainv, ray2, step2, tt2) + inner2
 
 
 def create_grid(type, **kwargs):

@@ -1,7 +1,9 @@
 """The training step of the dense-grid models and of FourierGridModel issued natively: ONE autograd node whose forward is two C calls
 (include/ugrid_hip.h: ugrid_voxgo_step_sample / _forward) and whose backward is one (ugrid_voxgo_step_backward), in place of the
-op-by-op step's four nodes and ~30 launches issued from Python (voxgo_model.py / fourier_model.py: TrainSampleVox / TrainSample, the
-k0 GridQuery, FusedRgbnet, RenderLoss).  The C side runs the same kernels on the same sizes in the same order, so loss, outputs and every gradient are the
+op-by-op step's four nodes and ~30 launches issued from Python (train_model.py and its subclasses in voxgo_model.py /
+fourier_model.py: TrainSampleVox / TrainSample, the k0 GridQuery, FusedRgbnet, RenderLoss).  The models reach it through
+TrainModel._native_params / _native_forward; its march scratch is grid.scratch, shared with those sample ops.
+The C side runs the same kernels on the same sizes in the same order, so loss, outputs and every gradient are the
 op-by-op step's (tests/test_gpu_voxgo_train.py, tests/test_gpu_train_step.py: bit for bit where sums have a fixed order); what changes is the host time between launches.
 
 Only the tensors a training loop reads come back as autograd outputs (loss; mse without gradient); the per-sample arrays of the
@@ -127,13 +129,7 @@ class VoxGOStep(torch.autograd.Function):
             raise RuntimeError("VoxGOStep: rgbnet weights must be [W, C+3+6pe], [W,W], [3,W]")
         if viewdirs.shape != (R, 3) or rays_d.shape != (R, 3) or target.shape != (R, 3) or (bg is not None and bg.shape != (R, 3)):
             raise RuntimeError("VoxGOStep: rays_o, rays_d, viewdirs, target must all be [R,3]")
-        key = (dev, R * S)
-        sc = _grid.TrainSampleVox._scratch.get(key)
-        if sc is None:
-            _grid.TrainSampleVox._scratch.clear()          # one ray-batch shape at a time: 32 B per (ray, slot)
-            sc = (torch.empty(R * S, 3, device=dev), torch.empty(R * S, device=dev), torch.empty(R * S, dtype=torch.int32, device=dev),
-                  torch.empty(R * S, device=dev), torch.empty(R * S, device=dev))
-            _grid.TrainSampleVox._scratch[key] = sc
+        sc = _grid.scratch(dev, R * S)          # the sample ops' scratch: this node's sampling half is theirs
         counts = torch.empty(2, R, dtype=torch.int32, device=dev)
         i64 = torch.empty(4 * R + 2, dtype=torch.int64, device=dev)        # offsets [2,R] | totals [2] | seg [2R]
         perray = torch.empty(R, 7, device=dev)                             # ray_tot [R,2] | partial [R,5]

@@ -10,7 +10,9 @@ Same functions, same return tuples and the same random streams here (numpy permu
 the 'random' mode), with the rays produced by the one-kernel `fourier_render.get_rays_of_a_view` when the poses live on the
 GPU.  On an MI355X the natural set-up is `load2gpu_on_the_fly = False`: 250 full-HD views are 500 M rays x 48 B = 25 GB of
 the 288 GB, so the ray table stays resident and a batch is four device-side row gathers -- no per-iteration H2D copy.
-NDC rays belong to the DirectMPIGO path (out of scope)."""
+NDC rays belong to the DirectMPIGO path (out of scope).
+
+Also the two ray-preparation utilities the models and DirectVoxGORenderer share, `voxel_count_views` and `hit_coarse_geo`."""
 import numpy as np
 import torch
 
@@ -162,3 +164,48 @@ def sample_batch(cfg_train, rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr, indexs_tr
     if load2gpu_on_the_fly:
         out = [t.to(device) if t is not None else None for t in out]
     return tuple(out)
+
+
+def voxel_count_views(query, xyz_min, xyz_max, voxel_size, world_size, count_shape, rays_o_tr, rays_d_tr, imsz, near, stepsize,
+                      downrate=1, irregular_shape=False):
+    """How many training views see each voxel of a plain grid of `world_size` over the box (dvgo.py:247-277,
+    FourierGrid_model.py:392-418): per image the trilinear footprint of its rays' samples is scattered into a zero grid -- by
+    the backward of `query`, a differentiable lookup (grid.GridQuery.apply or an injected one) -- and a voxel counts as seen
+    when it gathered more than 1.  Returns the counts as a float grid of `count_shape` (the model's density grid's)."""
+    far = 1e9
+    dev = xyz_min.device
+    n_samples = int(np.linalg.norm(world_size.cpu().numpy().astype(np.float64) + 1) / stepsize) + 1
+    rng = torch.arange(n_samples, device=dev)[None].float()
+    count = torch.zeros(count_shape, device=dev)
+    for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
+        ones = torch.zeros([1, 1] + world_size.tolist(), device=dev).requires_grad_(True)
+        if irregular_shape:
+            o_chunks, d_chunks = o_img.split(10000), d_img.split(10000)
+        else:
+            o_chunks = o_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
+            d_chunks = d_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
+        for o, d in zip(o_chunks, d_chunks):
+            o, d = o.to(dev), d.to(dev)
+            vec = torch.where(d == 0, torch.full_like(d, 1e-6), d)
+            t_min = torch.minimum((xyz_max - o) / vec, (xyz_min - o) / vec).amax(-1).clamp(min=near, max=far)
+            step = stepsize * voxel_size * rng
+            pts = o[..., None, :] + d[..., None, :] * (t_min[..., None] + step / d.norm(dim=-1, keepdim=True))[..., None]
+            query(ones, pts, xyz_min, xyz_max, 0).sum().backward()
+        with torch.no_grad():
+            count += (ones.grad > 1)
+    return count
+
+
+@torch.no_grad()
+def hit_coarse_geo(ru, rays_o, rays_d, xyz_min, xyz_max, near, stepdist, mask, xyz2ijk_scale, xyz2ijk_shift):
+    """bool [...]: does the ray pass through a cell the mask cache marks as possibly occupied? (dvgo.py:291-304)
+    ru: the render_utils_cuda module (sample_pts_on_rays, maskcache_lookup) or another implementation of it."""
+    far = 1e9
+    shape = rays_o.shape[:-1]
+    o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+    pts, outbbox, ray_id = ru.sample_pts_on_rays(o, d, xyz_min, xyz_max, near, far, stepdist)[:3]
+    inb = ~outbbox
+    occ = ru.maskcache_lookup(mask, pts[inb].contiguous(), xyz2ijk_scale, xyz2ijk_shift)
+    hit = torch.zeros(o.shape[0], dtype=torch.bool, device=o.device)
+    hit[ray_id[inb][occ]] = True
+    return hit.reshape(shape)

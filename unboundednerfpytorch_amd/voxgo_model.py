@@ -11,28 +11,24 @@ mask-cache tests, the density lookup, Raw2Alpha, both thresholds, Alphas2Weights
 (grid.TrainSampleVox), the k0 lookup is the channel-last kernel, the default 3 x 128 rgbnet runs on the fp32-MFMA kernels
 (ops.FusedRgbnet); `fused_forward = False` selects the op-by-op chain over the same drop-in ops (the A/B reference of the
 tests).  Inference should use dvgo_render.DirectVoxGORenderer / dcvgo_render.DirectContractedVoxGORenderer (fused render
-kernels).  There is no CPU path: the ops raise without the HIP library."""
+kernels).  There is no CPU path: the ops raise without the HIP library.
+
+What the two models share with FourierGridModel is train_model.TrainModel; _VoxGOBase adds the single resolution, the device-side
+mask vertices and the host copies of the kernels' by-value constants; each model keeps its constructor, its sampling and the
+keys of its return dict."""
 import math
 
 import numpy as np
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
 from . import grid as _grid
 from . import ops as _ops
+from .train_model import TrainModel, make_rgbnet
 
 
-def _make_rgbnet(dim0, width, depth):
-    net = nn.Sequential(nn.Linear(dim0, width), nn.ReLU(inplace=True),
-                        *[nn.Sequential(nn.Linear(width, width), nn.ReLU(inplace=True)) for _ in range(depth - 2)],
-                        nn.Linear(width, 3))
-    nn.init.constant_(net[-1].bias, 0)
-    return net
-
-
-class _VoxGOBase(nn.Module):
-    """What the two models share: one resolution for both grids, the mask cache, the coarse-to-fine step, the TV hooks."""
+class _VoxGOBase(TrainModel):
+    """What the two dense-grid models add to TrainModel: one resolution for both grids, the device-side mask vertices, the host
+    copies of the small buffers the kernels take by value."""
     fused_forward = True        # grid.TrainSampleVox (needs fast_color_thres > 0, like the reference's own masking branches)
     fused_rgbnet = True         # ops.FusedRgbnet for the default 3-layer rgbnet
     native_step = True          # native_step.VoxGOStep: the fused training forward + loss as ONE autograd node issued from C
@@ -45,16 +41,9 @@ class _VoxGOBase(nn.Module):
             raise NotImplementedError("only DenseGrid (TensoRFGrid is outside the hot path, SURVEY.md section 8)")
         self.density_type, self.k0_type = density_type, k0_type
         self.density_config, self.k0_config = density_config, k0_config
-        self.density = self._make_grid(1, None)
+        self.density = self._make_grid(1, self.world_size, False, None)
         self.k0_dim = k0_dim
-        self.k0 = self._make_grid(k0_dim, channels_last)
-
-    def _make_grid(self, channels, channels_last):
-        ws = self.world_size
-        numel = channels * int(ws[0]) * int(ws[1]) * int(ws[2])
-        cfg = {'channels_last': True} if (channels_last and channels > 1 and channels % 4 == 0 and numel < 2 ** 31) else None
-        return _grid.FourierGrid(channels=channels, world_size=ws, xyz_min=self.xyz_min, xyz_max=self.xyz_max,
-                                 use_nerf_pos=False, fourier_freq_num=0, config=cfg)
+        self.k0 = self._make_grid(k0_dim, self.world_size, False, channels_last)
 
     def _set_grid_resolution(self, num_voxels):
         self.num_voxels = num_voxels
@@ -71,21 +60,6 @@ class _VoxGOBase(nn.Module):
         axes = [torch.linspace(self.xyz_min[a], self.xyz_max[a], int(shape[a]), device=dev) for a in range(3)]
         return torch.stack(torch.meshgrid(*axes, indexing='ij'), -1)
 
-    def _new_mask(self, mask):
-        return _grid.MaskGrid(path=None, mask=mask, xyz_min=self.xyz_min, xyz_max=self.xyz_max)
-
-    def activate_density(self, density, interval=None):
-        interval = interval if interval is not None else self.voxel_size_ratio
-        return _ops.Raw2Alpha.apply(density.flatten(), self.act_shift, interval).reshape(density.shape)
-
-    def density_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.density.total_variation_add_grad(w, w, w, dense_mode)
-
-    def k0_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.k0.total_variation_add_grad(w, w, w, dense_mode)
-
     @torch.no_grad()
     def scale_volume_grid(self, num_voxels):
         """Coarse-to-fine step (dvgo.py:216-236, dcvgo.py:156-176): both grids resampled trilinearly, the mask cache rebuilt at the
@@ -93,19 +67,8 @@ class _VoxGOBase(nn.Module):
         self._set_grid_resolution(num_voxels)
         self.density.scale_volume_grid(self.world_size)
         self.k0.scale_volume_grid(self.world_size)
-        if np.prod(self.world_size.tolist()) <= 256 ** 3:
-            xyz = self._vertices(self.world_size.tolist())
-            alpha = F.max_pool3d(self.activate_density(self.density.get_dense_grid()), kernel_size=3, padding=1, stride=1)[0, 0]
-            self.mask_cache = self._new_mask(self.mask_cache(xyz) & (alpha > self.fast_color_thres)).to(xyz.device)
+        self._rebuild_mask_cache()
         self._hc_ver = None
-
-    @torch.no_grad()
-    def update_occupancy_cache(self):
-        """mask &= (3x3x3 max-pooled alpha at the cache's own vertices > fast_color_thres)  (dvgo.py:238-248, dcvgo.py:178-192)"""
-        xyz = self._vertices(self.mask_cache.mask.shape)
-        alpha = self.activate_density(self.density(xyz)[None, None])
-        alpha = F.max_pool3d(alpha, kernel_size=3, padding=1, stride=1)[0, 0]
-        self.mask_cache.mask &= (alpha > self.fast_color_thres)
 
     def __setattr__(self, name, value):
         # a replaced mask cache (scale_volume_grid, a checkpoint loader, user code) may reuse the id and the storage address of the
@@ -142,91 +105,11 @@ class _VoxGOBase(nn.Module):
             self._sc_key = key
         return self._sc
 
-    # names FourierGridModel uses for its two resolutions (train_step.train_iteration reads them)
-    @property
-    def world_size_density(self):
-        return self.world_size
-
-    @property
-    def world_size_rgb(self):
-        return self.world_size
-
-    def _can_fuse(self, rays_o):
-        return self.fused_forward and self.fast_color_thres > 0 and rays_o.is_cuda
-
-    def _native_params(self):
-        """The parameters of native_step.VoxGOStep (density grid, k0 grid, the rgbnet's three weights and biases), or None when this
-        configuration takes the op-by-op ops: the native step needs the default 3-layer rgbnet fed by all of k0 (rgbnet_direct),
-        gradients on, and every one of those parameters trainable."""
-        if not (self.native_step and self.fused_rgbnet and self.rgbnet is not None and torch.is_grad_enabled()
-                and getattr(self, 'rgbnet_direct', True)):
-            return None
-        lin = _ops.rgbnet_linears(self.rgbnet)
-        if lin is None:
-            return None
-        params = [self.density.grid, self.k0.grid] + [p for l in lin for p in (l.weight, l.bias)]
-        if not all(p.requires_grad for p in params) or self.density.query_fn is not None or self.k0.query_fn is not None \
-                or self.density.grid.shape[0] != 1 or self.k0.grid.shape[0] != 1:
-            return None
-        return params
-
-    def _const_bg(self, N, value, dev):
-        """the constant background colour as [N,3] rows (read-only; kept between steps: one fill launch less per iteration), or None
-        for a black background"""
-        if float(value) == 0.0:
-            return None
-        key = (int(N), float(value), str(dev))
-        cached = getattr(self, '_bg_rows', None)
-        if cached is None or cached[0] != key:
-            cached = (key, torch.full((N, 3), float(value), device=dev))
-            object.__setattr__(self, '_bg_rows', cached)
-        return cached[1]
-
-    def _native_forward(self, params, mode, cfg, t, rays_o, rays_d, viewdirs, fused_loss, bg):
-        """The training forward + loss as ONE autograd node issued from C (native_step.VoxGOStep): the reference's return dict with
-        loss / mse added, the per-sample arrays detached"""
-        from .native_step import VoxGOStep
-        pack = {'mode': mode, 'cfg': cfg, 't': t, 'rays_o': rays_o, 'rays_d': rays_d, 'viewdirs': viewdirs, 'viewfreq': self.viewfreq,
-                'xyz_min': self.xyz_min, 'xyz_max': self.xyz_max, 'k0_xyz_min': self.k0.xyz_min, 'k0_xyz_max': self.k0.xyz_max,
-                'mask': self.mask_cache.mask, 'target': fused_loss['target'], 'bg': bg, 'coef': fused_loss['coef'],
-                'sync_free': self.native_sync_free}
-        loss, mse = VoxGOStep.apply(*params, pack)
-        o = pack['out']
-        return {'alphainv_last': o['alphainv_last'], 'weights': o['weights'], 'rgb_marched': o['rgb_marched'], 'raw_alpha': o['raw_alpha'],
-                'raw_density': o['raw_density'], 'raw_logits': o['raw_logits'], 'ray_id': o['ray_id'], 'step_id': o['step_id'],
-                't': o['t'], 'loss': loss, 'mse': mse, 'loss_mse': o['loss_mse'], 'native': pack}
-
-    def _logits(self, k0_view, viewdirs, ray_id):
-        """rgbnet([k0, view embedding]) of the surviving samples: the fp32-MFMA kernels for the default 3-layer net while training"""
-        lin = _ops.rgbnet_linears(self.rgbnet) if (self.fused_rgbnet and k0_view.is_cuda and torch.is_grad_enabled()) else None
-        if lin is not None:
-            rows = _ops.ViewRows(viewdirs, self.viewfreq, ray_id)      # the embedding is formed inside, with the concatenation
-            return _ops.FusedRgbnet.apply(k0_view, rows, lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias)
-        emb = _ops.rgbnet_features(None, viewdirs, self.viewfreq, ray_id)
-        return self.rgbnet(torch.cat([k0_view, emb], -1))
-
-    def _fused_tail(self, fused_loss, k0, viewdirs, ray_id, residual, weights, alphainv_last, density, tt, bg, N):
-        """Training tail as ONE op (ops.RenderLoss): sigmoid, compositing, background and the loss terms of run_train.py:254-279.
-        train_step.train_iteration passes fused_loss = {'target': [N,3], 'coef': ops.loss_coefficients(...)}.  The colour logits are
-        the rgbnet's output (+ the diffuse channels of the residual model) or, in the coarse stage, the 3-channel k0 itself."""
-        if self.rgbnet is None:
-            logits = k0
-        elif residual:
-            logits = self._logits(k0[:, 3:].contiguous(), viewdirs, ray_id) + k0[:, :3]
-        else:
-            logits = self._logits(k0, viewdirs, ray_id)
-        dens = density if density is not None else torch.zeros_like(weights)
-        loss, mse, rgb_marched = _ops.RenderLoss.apply(logits.contiguous(), weights, alphainv_last, dens, ray_id, tt, None,
-                                                       fused_loss['target'], bg, fused_loss['coef'])
-        return logits, loss, mse, rgb_marched
-
-    def _colour(self, k0, viewdirs, ray_id, residual):
-        """rgb of the surviving samples (dvgo.py:377-398, dcvgo.py:332-344)"""
-        if self.rgbnet is None:
-            return torch.sigmoid(k0)
-        if residual:
-            return torch.sigmoid(self._logits(k0[:, 3:].contiguous(), viewdirs, ray_id) + k0[:, :3])
-        return torch.sigmoid(self._logits(k0, viewdirs, ray_id))
+    # names FourierGridModel uses for its two resolutions (TrainModel and train_step.train_iteration read them)
+    world_size_density = world_size_rgb = property(lambda self: self.world_size)
+    world_len_density = property(lambda self: self.world_len)
+    voxel_size_density = property(lambda self: self.voxel_size)
+    voxel_size_ratio_density = property(lambda self: self.voxel_size_ratio)
 
 
 class DirectVoxGO(_VoxGOBase):
@@ -264,7 +147,7 @@ class DirectVoxGO(_VoxGOBase):
         else:
             self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
             dim0 = 3 + 6 * viewbase_pe + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
-            self.rgbnet = _make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
+            self.rgbnet = make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
         self.mask_cache_path, self.mask_cache_thres = mask_cache_path, mask_cache_thres
         if mask_cache_world_size is None:
             mask_cache_world_size = self.world_size
@@ -297,45 +180,13 @@ class DirectVoxGO(_VoxGOBase):
         self.density.get_dense_grid()
         self.density.grid[nearest[None, None] <= near_clip] = -100
 
-    def voxel_count_views(self, rays_o_tr, rays_d_tr, imsz, near, far, stepsize, downrate=1, irregular_shape=False):
-        """How many training views see each voxel (dvgo.py:250-276): per image the trilinear footprint of its rays' samples is
-        scattered into a zero grid (the lookup's backward); a voxel counts as seen when it gathered more than 1."""
-        far = 1e9
-        dev = self.xyz_min.device
-        n_samples = int(np.linalg.norm(self.world_size.cpu().numpy().astype(np.float64) + 1) / stepsize) + 1
-        rng = torch.arange(n_samples, device=dev)[None].float()
-        count = torch.zeros(self.density.get_dense_grid().shape, device=dev)
-        for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
-            ones = torch.zeros([1, 1] + self.world_size.tolist(), device=dev).requires_grad_(True)
-            if irregular_shape:
-                o_chunks, d_chunks = o_img.split(10000), d_img.split(10000)
-            else:
-                o_chunks = o_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
-                d_chunks = d_img[::downrate, ::downrate].to(dev).flatten(0, -2).split(10000)
-            for o, d in zip(o_chunks, d_chunks):
-                o, d = o.to(dev), d.to(dev)
-                vec = torch.where(d == 0, torch.full_like(d, 1e-6), d)
-                rate_a, rate_b = (self.xyz_max - o) / vec, (self.xyz_min - o) / vec
-                t_min = torch.minimum(rate_a, rate_b).amax(-1).clamp(min=near, max=far)
-                step = stepsize * self.voxel_size * rng
-                pts = o[..., None, :] + d[..., None, :] * (t_min[..., None] + step / d.norm(dim=-1, keepdim=True))[..., None]
-                _grid.GridQuery.apply(ones, pts, self.xyz_min, self.xyz_max, 0).sum().backward()
-            with torch.no_grad():
-                count += (ones.grad > 1)
-        return count
-
     def hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         """Does a ray pass through known-occupied space? (dvgo.py:291-304)"""
         from . import render_utils_cuda
-        far = 1e9
-        shape = rays_o.shape[:-1]
-        rays_o, rays_d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
-        pts, outbbox, ray_id = render_utils_cuda.sample_pts_on_rays(rays_o, rays_d, self.xyz_min, self.xyz_max, near, far,
-                                                                    stepsize * self.voxel_size)[:3]
-        inb = ~outbbox
-        hit = torch.zeros([len(rays_o)], dtype=torch.bool, device=rays_o.device)
-        hit[ray_id[inb][self.mask_cache(pts[inb])]] = 1
-        return hit.reshape(shape)
+        from .train_rays import hit_coarse_geo
+        mc = self.mask_cache
+        return hit_coarse_geo(render_utils_cuda, rays_o, rays_d, self.xyz_min, self.xyz_max, near, stepsize * self.voxel_size, mc.mask,
+                              mc.xyz2ijk_scale, mc.xyz2ijk_shift)
 
     def sample_ray(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         """dvgo.py:306-330: the in-box samples of every ray, near to far: pts [M,3], ray_id [M], step_id [M]"""
@@ -360,8 +211,9 @@ class DirectVoxGO(_VoxGOBase):
             fl = render_kwargs.get('fused_loss')
             native = self._native_params() if (fl is not None and float(fl['coef'][2]) == 0.0 and float(fl['coef'][4]) == 0.0) else None
             if native is not None:
-                bg = self._const_bg(N, render_kwargs['bg'], rays_o.device)
-                out = self._native_forward(native, 'dvgo', cfg, None, rays_o.contiguous(), rays_d.contiguous(), viewdirs, fl, bg)
+                bg = self._bg_rows(N, rays_o.device, render_kwargs['bg'], cached=True)
+                out = self._native_forward(native, 'dvgo', cfg, None, rays_o.contiguous(), rays_d.contiguous(), viewdirs, fl, bg,
+                                           self.mask_cache.mask)
                 for k in ('raw_density', 'step_id', 't'):      # (not in DirectVoxGO's return dict, dvgo.py:405-417)
                     out.pop(k)
                 return out
@@ -386,29 +238,23 @@ class DirectVoxGO(_VoxGOBase):
         if k0.dim() == 1:
             k0 = k0.unsqueeze(-1)
         residual = self.rgbnet is not None and not self.rgbnet_direct
-        dev = rays_o.device
         fused_loss = render_kwargs.get('fused_loss')
         if fused_loss is not None and tt is not None and k0.is_cuda and float(fused_loss['coef'][2]) == 0.0 and float(fused_loss['coef'][4]) == 0.0:
             # (the bounded model has no `s` / `t`: configurations with the distortion or nearclip terms take the composed tail and
             # fail there exactly as they do with the reference's DirectVoxGO)
-            bg = torch.full((N, 3), float(render_kwargs['bg']), device=dev) if float(render_kwargs['bg']) != 0.0 else None
-            logits, loss, mse, rgb_marched = self._fused_tail(fused_loss, k0, viewdirs, ray_id, residual, weights, alphainv_last, density,
-                                                              tt, bg, N)
+            bg = self._bg_rows(N, rays_o.device, render_kwargs['bg'])
+            logits = self._colour_logits(k0, viewdirs, ray_id, residual)
+            loss, mse, rgb_marched = self._render_loss(fused_loss, logits, weights, alphainv_last, density, ray_id, tt, bg)
             return {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched, 'raw_alpha': alpha,
                     'raw_logits': logits, 'ray_id': ray_id, 'loss': loss, 'mse': mse}
-        rgb = self._colour(k0, viewdirs, ray_id, residual=residual)
-        rgb_marched = torch.zeros(N, 3, device=dev).index_add_(0, ray_id, weights.unsqueeze(-1) * rgb)
-        rgb_marched = rgb_marched + alphainv_last.unsqueeze(-1) * render_kwargs['bg']
-        out = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched, 'raw_alpha': alpha, 'raw_rgb': rgb,
-               'ray_id': ray_id}
-        if render_kwargs.get('render_depth', False):
-            with torch.no_grad():
-                out['depth'] = torch.zeros(N, device=dev).index_add_(0, ray_id, weights * step_id)
-        return out
+        rgb = torch.sigmoid(self._colour_logits(k0, viewdirs, ray_id, residual))
+        return self._composed_tail(N, rgb, alpha, weights, alphainv_last, ray_id, step_id, render_kwargs['bg'],
+                                   render_kwargs.get('render_depth', False))
 
 
 class DirectContractedVoxGO(_VoxGOBase):
     """The contracted-unbounded model (dcvgo.py:27-384)."""
+    table_end = 2.0             # sample_ray's inner samples span [0, 2] (dcvgo.py:243-250)
     fused_loss = True           # train_step.train_iteration: compositing + loss as ops.RenderLoss (the losses of run_train.py:254-279)
 
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None, mask_cache_world_size=None,
@@ -438,7 +284,7 @@ class DirectContractedVoxGO(_VoxGOBase):
             self.rgbnet = None
         else:
             self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
-            self.rgbnet = _make_rgbnet(3 + 6 * viewbase_pe + self.k0_dim, rgbnet_width, rgbnet_depth)
+            self.rgbnet = make_rgbnet(3 + 6 * viewbase_pe + self.k0_dim, rgbnet_width, rgbnet_depth)
         if mask_cache_world_size is None:
             mask_cache_world_size = self.world_size
         self.mask_cache = self._new_mask(torch.ones([int(x) for x in mask_cache_world_size], dtype=torch.bool))
@@ -463,22 +309,6 @@ class DirectContractedVoxGO(_VoxGOBase):
             count += (ones.grad > 1)
         self.mask_cache.mask &= (count >= maskout_lt_nviews)[0, 0]
 
-    def _sample_table(self, stepsize):
-        """the mid-point sample distances of sample_ray (dcvgo.py:243-250), [S] on the host"""
-        n_inner = int(2 / (2 + 2 * self.bg_len) * self.world_len / stepsize) + 1
-        b_inner = torch.linspace(0, 2, n_inner + 1)
-        b_outer = 2 / torch.linspace(1, 1 / 128, n_inner + 1)
-        return torch.cat([(b_inner[1:] + b_inner[:-1]) * 0.5, (b_outer[1:] + b_outer[:-1]) * 0.5])
-
-    def sample_table(self, stepsize, device):
-        key = (float(stepsize), int(self.world_len), str(device))
-        cached = getattr(self, '_t_cache', None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        t = self._sample_table(stepsize).to(device)
-        self._t_cache = (key, t)
-        return t
-
     def sample_ray(self, ori_rays_o, ori_rays_d, stepsize, is_train=False, **render_kwargs):
         """dcvgo.py:228-263: [N,S,3] points (contracted outside the unit cube / ball), inner_mask [N,S], t [S]"""
         o = (ori_rays_o - self.scene_center) / self.scene_radius
@@ -500,6 +330,7 @@ class DirectContractedVoxGO(_VoxGOBase):
         interval = stepsize * self.voxel_size_ratio
         dist_thres = (2 + 2 * self.bg_len) / self.world_len * stepsize * 0.95
         dev = rays_o.device
+        bg = 'rand' if (render_kwargs.get('rand_bkgd', False) and is_train) else render_kwargs['bg']
         if self._can_fuse(rays_o):
             hc = self._host_consts()
             t = self.sample_table(stepsize, dev)
@@ -511,11 +342,9 @@ class DirectContractedVoxGO(_VoxGOBase):
             fl = render_kwargs.get('fused_loss')
             native = self._native_params() if fl is not None else None
             if native is not None:
-                if render_kwargs.get('rand_bkgd', False) and is_train:
-                    bg = torch.rand(N, 3, device=dev)
-                else:
-                    bg = self._const_bg(N, render_kwargs['bg'], dev)
-                out = self._native_forward(native, 'dcvgo', cfg, t, rays_o.contiguous(), rays_d.contiguous(), viewdirs, fl, bg)
+                bg = self._bg_rows(N, dev, bg, cached=True)
+                out = self._native_forward(native, 'dcvgo', cfg, t, rays_o.contiguous(), rays_d.contiguous(), viewdirs, fl, bg,
+                                           self.mask_cache.mask)
                 out['n_max'] = n_max
                 return out
             pts, density, alpha, weights, alphainv_last, ray_id, step_id, tt, inner = _grid.TrainSampleVox.apply(
@@ -547,27 +376,14 @@ class DirectContractedVoxGO(_VoxGOBase):
             k0 = k0.unsqueeze(-1)
         fused_loss = render_kwargs.get('fused_loss')
         if fused_loss is not None and k0.is_cuda:
-            if render_kwargs.get('rand_bkgd', False) and is_train:
-                bg = torch.rand(N, 3, device=dev)
-            else:
-                bg = torch.full((N, 3), float(render_kwargs['bg']), device=dev) if float(render_kwargs['bg']) != 0.0 else None
-            logits, loss, mse, rgb_marched = self._fused_tail(fused_loss, k0, viewdirs, ray_id, False, weights, alphainv_last, density, tt,
-                                                              bg, N)
+            bg = self._bg_rows(N, dev, bg)
+            logits = self._colour_logits(k0, viewdirs, ray_id)
+            loss, mse, rgb_marched = self._render_loss(fused_loss, logits, weights, alphainv_last, density, ray_id, tt, bg)
             return {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched, 'raw_density': density,
                     'raw_alpha': alpha, 'raw_logits': logits, 'ray_id': ray_id, 'step_id': step_id, 'n_max': n_max, 't': tt,
                     'loss': loss, 'mse': mse}
-        rgb = self._colour(k0, viewdirs, ray_id, residual=False)
-        rgb_marched = torch.zeros(N, 3, device=dev).index_add_(0, ray_id, weights.unsqueeze(-1) * rgb)
-        if render_kwargs.get('rand_bkgd', False) and is_train:
-            rgb_marched = rgb_marched + alphainv_last.unsqueeze(-1) * torch.rand_like(rgb_marched)
-        else:
-            rgb_marched = rgb_marched + alphainv_last.unsqueeze(-1) * render_kwargs['bg']
-        wsum_mid = torch.zeros(N, device=dev).index_add_(0, ray_id[inner], weights[inner])
-        s = 1 - 1 / (1 + tt)
-        out = {'alphainv_last': alphainv_last, 'weights': weights, 'wsum_mid': wsum_mid, 'rgb_marched': rgb_marched,
-               'raw_density': density, 'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id, 'step_id': step_id, 'n_max': n_max,
-               't': tt, 's': s}
-        if render_kwargs.get('render_depth', False):
-            with torch.no_grad():
-                out['depth'] = torch.zeros(N, device=dev).index_add_(0, ray_id, weights * s)
+        rgb = torch.sigmoid(self._colour_logits(k0, viewdirs, ray_id))
+        out = self._composed_tail(N, rgb, alpha, weights, alphainv_last, ray_id, step_id, bg,
+                                  render_kwargs.get('render_depth', False), contracted=(density, n_max, tt))
+        out['wsum_mid'] = torch.zeros(N, device=dev).index_add_(0, ray_id[inner], weights[inner])
         return out
