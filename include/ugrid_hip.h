@@ -632,6 +632,23 @@ int ugrid_tune(const char *key, int value);
 int ugrid_render_stats(void *ws, int64_t n_rays, int32_t n_samples, int64_t *d_stats,
                        ugrid_stream_t stream);
 
+/* Image metrics of a rendered frame against its ground truth, on the device (csrc/ugrid_metrics.hip): the arithmetic of
+ * numpy's np.sum(np.square(img - gt)) and of the reference's utils.rgb_ssim (FourierGrid/utils.py:79-125) on float32 images.
+ * img, gt: H x W pixels of 3 consecutive floats, pixel p at img + p * img_stride (stride in floats, >= 3: 3 for an [H,W,3]
+ * image, 5 for the rgb columns of the frame loop's packed [H*W,5] result).
+ *   out[0] = sum over the H*W*3 elements of (img - gt)^2: difference and square in fp32, the sum in fp64;
+ *   out[1] = sum over the [(H-10),(W-10),3] SSIM map (11-tap Gaussian, "valid" mode; products of the inputs in fp32, everything
+ *            behind them in fp64 with IEEE sqrt and division; c1 = (k1 max_val)^2, c2 = (k2 max_val)^2);
+ *   map    = NULL, or [(H-10),(W-10),3] doubles: the map itself, fully written.
+ * ws: ugrid_frame_metrics_ws_bytes(H, W) bytes = one {squared-error, ssim} pair of doubles (16 bytes) per 32 x 54 tile of the
+ * map, ceil((H-10)/32) * ceil((W-10)/54) tiles, fully written before it is read (0 for a frame the entry point refuses).  The
+ * tiles' pairs are added in a fixed order: two calls on the same inputs give the same bits.
+ * Returns hipErrorInvalidValue, before anything touches the device, for H < 11, W < 11 or filter_size != 11 (the one size built). */
+int64_t ugrid_frame_metrics_ws_bytes(int64_t H, int64_t W);
+int ugrid_frame_metrics(const float *img, int64_t img_stride, const float *gt, int64_t gt_stride, int64_t H,
+                        int64_t W, int32_t filter_size, double filter_sigma, double k1, double k2,
+                        double max_val, double *out, double *map, void *ws, ugrid_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UGRID_LIB") or os.path.join(_HERE, "libugrid_hip.so")  # UGRID_LIB: A/B builds only
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _c = ctypes
 _P = _c.c_void_p
@@ -177,6 +177,8 @@ _SIGNATURES = {
     "ugrid_tune": (_I, [_c.c_char_p, _I]),
     "ugrid_shade_supported": (_I, [_c.c_int32, _c.c_int32, _c.c_int32]),
     "ugrid_render_stats": (_I, [_P, _L, _c.c_int32, _P, _P]),
+    "ugrid_frame_metrics_ws_bytes": (_L, [_L, _L]),
+    "ugrid_frame_metrics": (_I, [_P, _L, _P, _L, _L, _L, _c.c_int32, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

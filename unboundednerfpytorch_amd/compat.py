@@ -45,3 +45,14 @@ def install_model_classes(package="FourierGrid"):
     if rt is not None and hasattr(rt, "FourierGridModel"):       # already imported: rebind its by-name import too
         rt.FourierGridModel = fourier_model.FourierGridModel
     return orig
+
+
+def install_metrics(utils_module):
+    """Set `utils_module.rgb_ssim` (the reference's FourierGrid.utils, or any module object with that attribute) to this package's
+    metrics.rgb_ssim -- same positional signature, evaluated by the HIP kernel -- so that the reference's own
+    run_render.render_viewpoints(..., eval_ssim=True) (run_render.py:77-78 calls utils.rgb_ssim(rgb, gt, max_val=1)) scores its
+    frames on the GPU.  Returns the function it replaced (setattr it back to restore)."""
+    from . import metrics
+    orig = getattr(utils_module, "rgb_ssim", None)
+    utils_module.rgb_ssim = metrics.rgb_ssim
+    return orig

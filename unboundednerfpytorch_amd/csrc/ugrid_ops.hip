@@ -10,7 +10,7 @@
 // file:line citations are in include/ugrid_hip.h.
 #include "ugrid_common.h"
 
-extern "C" int ugrid_abi_version(void) { return 2; }  // 2: ugrid_render_params.mlp_mode, ugrid_pack_mlp(k0_absmax, best_mode)
+extern "C" int ugrid_abi_version(void) { return 3; }  // 2: ugrid_render_params.mlp_mode, ugrid_pack_mlp(k0_absmax, best_mode); 3: ugrid_frame_metrics
 extern "C" const char *ugrid_target_arch(void) { return "gfx950"; }
 
 // ----------------------------------------------------------------------------------------------

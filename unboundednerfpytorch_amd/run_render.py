@@ -9,14 +9,15 @@ a side stream, overlapped with the next frame's render.  The views of a list are
 issued on two alternating streams, each with a work list of its own (frames_in_flight = 2), so that the march of view k + 1
 runs beside the shade of view k -- whole frames at 1080p: 8.8 -> 8.4 ms per view on white-noise grids, 14.0 -> 12.4 ms on
 a trained-like truck-shaped scene, every frame bit-identical (profiles/r06/frame_pair_n1.txt).  Same return values as the
-reference: numpy arrays rgbs [N,H,W,3], depths [N,H,W,1], bgmaps [N,H,W,1] (+ PSNRs when ground truth is given)."""
+reference: numpy arrays rgbs [N,H,W,3], depths [N,H,W,1], bgmaps [N,H,W,1] (+ PSNRs when ground truth is given; + SSIMs with
+eval_ssim, the reference's --eval_ssim: scored on the device by metrics.frame_metrics, on the stream that rendered the view)."""
 import numpy as np
 import torch
 
 
 @torch.no_grad()
 def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, render_factor=0,
-                      flip_x=False, flip_y=False, group=None, verbose=False, frames_in_flight=None):
+                      flip_x=False, flip_y=False, group=None, verbose=False, frames_in_flight=None, eval_ssim=False):
     """model: FourierGridRenderer, or a DirectVoxGORenderer / DirectContractedVoxGORenderer (their render_view takes the
     reference's render_kwargs 'near', 'far', 'bg' as well); render_poses [N,3or4,4] camera-to-world; HW [N,2]; Ks [N,3,3];
     render_kwargs: needs 'stepsize', may carry 'inverse_y' (the keys run_render.py passes; others are ignored).
@@ -24,13 +25,34 @@ def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, 
     n work lists in turn (renderers with use_workspace_slot; every further work list costs up to 8.4 GB at 1080p x 256 samples),
     1 = one stream.  2 is within 2 % of the best for 1080p frames; a view that leaves most of the chip idle gains from 4
     (DirectVoxGO, 800 x 800: 1.88 / 1.03 / 0.78 ms per view at 1 / 2 / 4; profiles/r06/frames_in_flight_sweep.txt).
-    Returns (rgbs, depths, bgmaps) or (rgbs, depths, bgmaps, psnrs) when gt_imgs is given."""
+    eval_ssim (needs gt_imgs and render_factor == 0, ValueError otherwise -- the reference skips the metric silently): view i's
+    ground truth is uploaded on the stream that renders view i and ugrid_frame_metrics runs there right behind the render, reading
+    the rgb columns of the packed result in place; the sums of all views land in one [N,2] device tensor that is read once, after the
+    loop.  The ground truth comes from pageable host memory, so each upload blocks the HOST for the duration of the copy (the
+    device keeps rendering the view queued just before); one ground-truth buffer and one scratch per view in flight.  With a
+    process group every rank scores the assembled frame.
+    Returns (rgbs, depths, bgmaps), (rgbs, depths, bgmaps, psnrs) when gt_imgs is given, or (rgbs, depths, bgmaps, psnrs, ssims)
+    with eval_ssim: ssims[i] is a Python float, the mean of view i's SSIM map (= metrics.rgb_ssim(rgbs[i], gt_imgs[i], 1)).
+    psnrs is computed on the host from the returned frames in every case."""
+    if eval_ssim:
+        if gt_imgs is None:
+            raise ValueError("eval_ssim needs gt_imgs")
+        if render_factor != 0:
+            raise ValueError("eval_ssim needs render_factor == 0 (the ground truth has the full frame's size)")
+        if len(gt_imgs) != len(render_poses):
+            raise ValueError("eval_ssim: %d ground-truth images for %d views" % (len(gt_imgs), len(render_poses)))
     assert len(render_poses) == len(HW) and len(HW) == len(Ks)
     HW = np.asarray(HW).copy()
     Ks = np.asarray(Ks, dtype=np.float64).copy()
     if render_factor != 0:                                    # run_render.py:22-26
         HW = (HW / render_factor).astype(int)
         Ks[:, :2, :3] /= render_factor
+    if eval_ssim:
+        for i in range(len(HW)):
+            if tuple(np.shape(gt_imgs[i])) != (int(HW[i][0]), int(HW[i][1]), 3):
+                raise ValueError("gt_imgs[%d] is %s, view %d is %d x %d" % (i, tuple(np.shape(gt_imgs[i])), i, HW[i][0], HW[i][1]))
+            if min(int(HW[i][0]), int(HW[i][1])) < 11:
+                raise ValueError("eval_ssim: view %d is %d x %d, the 11-tap SSIM window needs 11 x 11" % (i, HW[i][0], HW[i][1]))
     dev = model.device
     if frames_in_flight is None:
         frames_in_flight = int(getattr(model, "frames_in_flight", 2))
@@ -45,11 +67,19 @@ def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, 
     host = [None] * n_slots       # pinned buffers (one per view in flight), re-allocated when the frame size changes
     done = [None] * n_slots
     frames = []
+    if eval_ssim:
+        from . import metrics
+        sums = torch.empty((n, 2), dtype=torch.float64, device=dev)   # (written on the views' streams; the caller's stream joins them before the read)
+        gt_dev = [None] * n_slots   # per view in flight: ground truth [>= H*W*3] and the kernel's scratch, both allocated on the
+        gt_ws = [None] * n_slots    # slot's stream and re-used there in stream order
+        gt_src = [None] * n       # the host arrays being uploaded, held until their view is drained
 
-    def drain(slot, H, W):
+    def drain(slot, H, W, view):
         done[slot].synchronize()
         a = host[slot][: H * W * 5].numpy().reshape(H, W, 5).copy()
         frames.append(a)
+        if eval_ssim:
+            gt_src[view] = None
 
     pending = []                  # (slot, H, W) of copies in flight, oldest first
     for i in range(n):
@@ -62,7 +92,19 @@ def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, 
                 stream.wait_stream(caller)        # (whatever prepared the model -- bricks, weight images -- ran on the caller's stream)
         with torch.cuda.stream(stream):
             packed = _render_packed(model, H, W, Ks[i], render_poses[i], render_kwargs, flip_x, flip_y, group)
-            ready = stream.record_event()
+            if eval_ssim:
+                slot = i % n_slots
+                g = np.ascontiguousarray(np.asarray(gt_imgs[i]), dtype=np.float32)
+                need = metrics.workspace_bytes(H, W)
+                if gt_dev[slot] is None or gt_dev[slot].numel() < g.size:
+                    gt_dev[slot] = torch.empty(g.size, dtype=torch.float32, device=dev)
+                if gt_ws[slot] is None or gt_ws[slot].numel() < need:
+                    gt_ws[slot] = torch.empty(need, dtype=torch.uint8, device=dev)
+                gt_src[i] = g
+                gt_dev[slot][: g.size].copy_(torch.from_numpy(g).reshape(-1), non_blocking=True)
+                metrics.frame_metrics(packed.view(H * W, 5), gt_dev[slot][: g.size].view(H * W, 3), max_val=1.0, out=sums[i],
+                                      H=H, W=W, ws=gt_ws[slot])
+            ready = stream.record_event()       # (behind the metric: a drained slot's ground truth and scratch are free again)
         slot = i % n_slots
         if len(pending) == n_slots:     # the buffer about to be re-used must have been read out
             drain(*pending.pop(0))
@@ -73,7 +115,7 @@ def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, 
             host[slot][: packed.numel()].copy_(packed, non_blocking=True)
             packed.record_stream(copy_stream)
             done[slot] = copy_stream.record_event()
-        pending.append((slot, H, W))
+        pending.append((slot, H, W, i))
         if verbose:
             print("render_viewpoints: frame %d/%d queued (%dx%d)" % (i + 1, n, W, H))
     while pending:
@@ -82,7 +124,12 @@ def render_viewpoints(model, render_poses, HW, Ks, render_kwargs, gt_imgs=None, 
         model.use_workspace_slot(0)
         for st in pair:
             caller.wait_stream(st)
-    return _stack(frames, gt_imgs, render_factor, n)
+    res = _stack(frames, gt_imgs, render_factor, n)
+    if not eval_ssim:
+        return res
+    host_sums = sums.cpu().numpy()        # the one read of the metric (the caller's stream has joined every view's stream above)
+    ssims = [metrics.mean_ssim(host_sums[i, 1], int(HW[i][0]), int(HW[i][1])) for i in range(n)]
+    return res + (ssims,)
 
 
 def _render_packed(model, H, W, K, c2w, render_kwargs, flip_x, flip_y, group):
