@@ -503,7 +503,14 @@ int ugrid_train_sample_backward(int64_t n_rays, float act_shift, float interval,
  *       100-260: per-ray t_min / t_max / step count; `far` as the caller passes it, the model passes 1e9), ~mask_outbbox, the mask
  *       cache, then as above.  slots_per_ray = scratch slots per ray, >= the longest possible ray (the box diagonal / stepdist + 2).
  *   ugrid_train_sample_compact_vox = ugrid_train_sample_compact + inner2 [M2] bytes (dcvgo.py:262 inner_mask of the surviving
- *       samples; NULL: not wanted) and t_table == NULL allowed (DirectVoxGO has none: t2 receives float(step_id)). */
+ *       samples; NULL: not wanted) and t_table == NULL allowed (DirectVoxGO has none: t2 receives float(step_id)).
+ *   ugrid_train_sample_mpi    DirectMPIGO.forward's sampling (dmpigo.py:224-292): sample_ndc_pts_on_rays (render_utils_kernel.cu:245-270:
+ *       every ray takes the same n_steps >= 2 samples o + d * (j / (n_steps - 1)), d not normalised; n_steps scratch slots per ray),
+ *       ~mask_outbbox, the mask cache, density = dense trilinear lookup + act_shift(p) -- the per-plane shift, a lerp along z of the
+ *       `act_shift` table ([mpi_depth] floats ON THE DEVICE, mpi_depth <= 256: the [1,1,1,1,D] grid itself, nothing is read back) --,
+ *       Raw2Alpha with shift 0, then as above.  scratch_density holds the SUM: ugrid_train_sample_compact_vox (t_table NULL, inner2
+ *       NULL) and ugrid_train_sample_backward take act_shift = 0 and recompute the forward's exp.  No gradient reaches the table
+ *       (requires_grad False in the reference, dmpigo.py:50). */
 int ugrid_train_sample_dcvgo(const float *density_grid, int X, int Y, int Z, const float *rays_o, const float *rays_d,
                              int64_t n_rays, const float *t_table, int32_t n_samples, const float *scene_center3,
                              const float *scene_radius3, const float *xyz_min, const float *xyz_max, double bg_len, int norm_l2,
@@ -517,6 +524,14 @@ int ugrid_train_sample_dvgo(const float *density_grid, int X, int Y, int Z, cons
                             const float *xyz2ijk_shift3, float act_shift, float interval, float thres, float *scratch_pts,
                             float *scratch_density, int32_t *scratch_step, float *scratch_w, float *scratch_T, int32_t *count,
                             int32_t *count2, float *alphainv_last, ugrid_stream_t stream);
+int ugrid_train_sample_mpi(const float *density_grid, int X, int Y, int Z, const float *rays_o, const float *rays_d,
+                           int64_t n_rays, int32_t n_steps, const float *xyz_min, const float *xyz_max,
+                           const float *act_shift /* DEVICE [mpi_depth] */, int32_t mpi_depth,
+                           const uint8_t *mask, const int32_t *mask_dims3, const float *xyz2ijk_scale3,
+                           const float *xyz2ijk_shift3, float interval, float thres,
+                           float *scratch_pts, float *scratch_density, int32_t *scratch_step, float *scratch_w,
+                           float *scratch_T, int32_t *count, int32_t *count2, float *alphainv_last,
+                           ugrid_stream_t stream);
 int ugrid_train_sample_compact_vox(int64_t n_rays, int32_t slots_per_ray, float act_shift, float interval, float thres,
                                    const float *scratch_pts, const float *scratch_density, const int32_t *scratch_step,
                                    const float *scratch_w, const float *scratch_T, const int32_t *count, const int64_t *offset_end,

@@ -47,6 +47,20 @@ def install_model_classes(package="FourierGrid"):
     return orig
 
 
+def install_mpi_model_class(package="FourierGrid"):
+    """Rebind `<package>.dmpigo.DirectMPIGO` -- the model create_new_model builds for forward-facing scenes (cfg.data.ndc,
+    run_train.py:19-56) and run_train.py:190 dispatches on -- to mpi_model.DirectMPIGO, as install_model_classes does for the other
+    three.  Same calling order (after install_as_reference_extensions(), the reference tree on sys.path); a `<package>.run_train`
+    that is already imported has its module reference `dmpigo` in common, so nothing else needs rebinding.  Returns the original
+    class (to restore it: setattr it back)."""
+    import importlib
+    from . import mpi_model
+    dm = importlib.import_module(package + ".dmpigo")
+    orig = dm.DirectMPIGO
+    dm.DirectMPIGO = mpi_model.DirectMPIGO
+    return orig
+
+
 def install_metrics(utils_module):
     """Set `utils_module.rgb_ssim` (the reference's FourierGrid.utils, or any module object with that attribute) to this package's
     metrics.rgb_ssim -- same positional signature, evaluated by the HIP kernel -- so that the reference's own

@@ -348,9 +348,16 @@ struct ug_train_args {
 //   2 = DirectVoxGO (dvgo.py:306-400): per-ray box clipping and step count (infer_t_minmax / infer_n_samples /
 //       sample_pts_on_rays, render_utils_kernel.cu:16-57,100-260), mask_outbbox, the mask cache; a.S = slots per ray (>= the
 //       longest possible ray: the host sizes it for the box diagonal), t_table unused
+//   3 = DirectMPIGO (dmpigo.py:224-292): NDC rays, every ray takes the same a.S samples p = o + d * (j / (S-1)) with the direction NOT
+//       normalised (sample_ndc_pts_on_rays, render_utils_kernel.cu:245-270; the arithmetic of ug_march_tile_mpi), mask_outbbox, the
+//       mask cache; density = the grid lookup + the per-plane shift, a lerp along z of the D-entry table `plane_shift` (DEVICE memory:
+//       the act_shift grid itself, no host copy), the two added in fp32 like `self.density(p) + self.act_shift(p)`.  s_dens keeps
+//       the SUM and a.shift is 0, so the compaction and k_train_sample_bwd recompute the same exp; t_table unused
 struct ug_train_vox : ug_mask_args {      // the mask cache: ug_mask_lookup (ugrid_render.h), shared with the render march
   float dist_thres;                 // mode 1
   float near, far, stepdist;        // mode 2
+  const float *plane_shift;         // mode 3: [D]
+  int32_t D;                        // mode 3: mpi_depth
 };
 
 // sample t of a normalised ray, contracted outside the unit cube / ball (dcvgo.py:251-262, the arithmetic of k_train_march);
@@ -488,7 +495,7 @@ k_train_march(ug_train_args a, const float *__restrict__ grid, const float *__re
   }
 }
 
-// k_train_march<true> for the two dense-grid models (ug_train_vox above): MODE 1 = DirectContractedVoxGO, 2 = DirectVoxGO.
+// k_train_march<true> for the dense-grid models (ug_train_vox above): MODE 1 = DirectContractedVoxGO, 2 = DirectVoxGO, 3 = DirectMPIGO.
 // Same slot / scratch contract and the same stage-2 recurrence; P = 1, F = 0.
 template <int MODE>
 __global__ void __launch_bounds__(256)
@@ -509,6 +516,9 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
     ox = (rox - a.cx) / a.rx; oy = (roy - a.cy) / a.ry; oz = (roz - a.cz) / a.rz;
     const float dn = ug_norm3_torch(rdx, rdy, rdz);
     dx = rdx / dn; dy = rdy / dn; dz = rdz / dn;
+  } else if (MODE == 3) {
+    ox = rox; oy = roy; oz = roz;
+    dx = rdx; dy = rdy; dz = rdz;
   } else {
     // ray / box slab test; a zero direction component is replaced by float(1e-6) (infer_t_minmax)
     const float vx = (rdx == 0.f) ? (float)1e-6 : rdx, vy = (rdy == 0.f) ? (float)1e-6 : rdy, vz = (rdz == 0.f) ? (float)1e-6 : rdz;
@@ -528,6 +538,7 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
   float T_cum = 1.f;         // wave-uniform
   float cum = 0.f;           // wave-uniform: the cumdist_thres carry (MODE 1)
   bool stopped = false;
+  const float nm1 = (float)(a.S - 1), dm1 = (float)(v.D - 1);      // mode 3
   for (int j0 = 0; j0 < n && !stopped; j0 += UG_WAVE) {
     const int j = j0 + lane;
     bool keep = false, inner = true;
@@ -553,7 +564,7 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
       keep = j < n && (inner || over);
     } else {
       if (j < n) {
-        const float dist = v.stepdist * (float)j;
+        const float dist = MODE == 3 ? (float)j / nm1 : v.stepdist * (float)j;
         px = ox + dx * dist; py = oy + dy * dist; pz = oz + dz * dist;
         keep = !((lox > px) | (loy > py) | (loz > pz) | (hix < px) | (hiy < py) | (hiz < pz));   // ~mask_outbbox
       }
@@ -566,6 +577,17 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
 #pragma unroll
       for (int c = 0; c < 8; ++c) acc += grid[tp.off[c]] * tp.w[c];
       dens = acc;
+      if (MODE == 3) {
+        // act_shift(p), restated from ug_march_tile_mpi (ugrid_render.h: "act_shift: uz in [-1, 1] ..."): v0 * w0 + v1 * w1 as
+        // grid_sample forms it, a corner beyond the last plane not added.  The table is read from global memory: 1 KiB at most, two
+        // dwords per kept sample next to eight grid corners, and the waves of a block leave independently (no barrier to stage it)
+        const float iz = ((uz + 1.f) / 2.f) * dm1;
+        const float f0 = floorf(iz);
+        const int i0 = min(max((int)f0, 0), v.D - 1);
+        float sh = v.plane_shift[i0] * ((f0 + 1.f) - iz);
+        if (i0 + 1 < v.D) sh = sh + v.plane_shift[i0 + 1] * (iz - f0);
+        dens = acc + sh;
+      }
       float e;
       alpha = ug_train_alpha(dens, a.shift, a.interval, &e);
       keep = alpha > a.thres;
@@ -794,6 +816,7 @@ static int ug_fill_train_vox(ug_train_vox *v, const uint8_t *mask, const int32_t
                              const float *xyz2ijk_shift3) {
   if (!mask_dims3) return (int)hipErrorInvalidValue;
   v->dist_thres = 0.f; v->near = 0.f; v->far = 0.f; v->stepdist = 1.f;
+  v->plane_shift = nullptr; v->D = 1;
   return ug_fill_mask_args(*v, mask, mask_dims3[0], mask_dims3[1], mask_dims3[2], xyz2ijk_scale3, xyz2ijk_shift3);
 }
 
@@ -843,6 +866,30 @@ extern "C" int ugrid_train_sample_dvgo(const float *density_grid, int X, int Y, 
   a.cx = a.cy = a.cz = 0.f; a.rx = a.ry = a.rz = 1.f; a.B = 1.f; a.A = 0.f;
   a.shift = act_shift; a.interval = interval; a.thres = thres;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_vox<2>), dim3(ug_blocks(n_rays * UG_WAVE, 256)), dim3(256), 0, ST(s), a, v, density_grid,
+                     rays_o, rays_d, (const float *)nullptr, xyz_min, xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w,
+                     scratch_T, count2, alphainv_last);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_train_sample_mpi(const float *density_grid, int X, int Y, int Z, const float *rays_o, const float *rays_d,
+                                      int64_t n_rays, int32_t n_steps, const float *xyz_min, const float *xyz_max,
+                                      const float *act_shift, int32_t mpi_depth, const uint8_t *mask, const int32_t *mask_dims3,
+                                      const float *xyz2ijk_scale3, const float *xyz2ijk_shift3, float interval, float thres,
+                                      float *scratch_pts, float *scratch_density, int32_t *scratch_step, float *scratch_w,
+                                      float *scratch_T, int32_t *count, int32_t *count2, float *alphainv_last, ugrid_stream_t s) {
+  if (n_rays <= 0) return 0;
+  if (n_steps < 2 || !act_shift || mpi_depth < 1 || mpi_depth > 256 || !scratch_w || !scratch_T || !count2 || !alphainv_last)
+    return (int)hipErrorInvalidValue;
+  ug_train_vox v;
+  const int rc = ug_fill_train_vox(&v, mask, mask_dims3, xyz2ijk_scale3, xyz2ijk_shift3);
+  if (rc) return rc;
+  v.plane_shift = act_shift; v.D = mpi_depth;
+  ug_train_args a;
+  a.n_rays = n_rays; a.S = n_steps; a.P = 1; a.F = 0; a.X = X; a.Y = Y; a.Z = Z; a.norm_l2 = 0;
+  a.cx = a.cy = a.cz = 0.f; a.rx = a.ry = a.rz = 1.f; a.B = 1.f; a.A = 0.f;
+  a.shift = 0.f; a.interval = interval; a.thres = thres;      // the per-plane shift is part of the stored density
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_vox<3>), dim3(ug_blocks(n_rays * UG_WAVE, 256)), dim3(256), 0, ST(s), a, v, density_grid,
                      rays_o, rays_d, (const float *)nullptr, xyz_min, xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w,
                      scratch_T, count2, alphainv_last);
   UG_LAUNCH_CHECK();

@@ -223,17 +223,19 @@ class TrainSample(torch.autograd.Function):
 
 
 class TrainSampleVox(TrainSample):
-    """TrainSample for the reference's two dense-grid models: the sampling of DirectContractedVoxGO.forward (dcvgo.py:228-330,
-    cfg['mode'] == 'dcvgo') and of DirectVoxGO.forward (dvgo.py:306-375, 'dvgo') as one march + one compaction
-    (include/ugrid_hip.h: ugrid_train_sample_dcvgo / _dvgo / _compact_vox), differentiable in the density grid through
+    """TrainSample for the reference's dense-grid models: the sampling of DirectContractedVoxGO.forward (dcvgo.py:228-330,
+    cfg['mode'] == 'dcvgo'), of DirectVoxGO.forward (dvgo.py:306-375, 'dvgo') and of DirectMPIGO.forward (dmpigo.py:224-292, 'mpi')
+    as one march + one compaction (include/ugrid_hip.h: ugrid_train_sample_dcvgo / _dvgo / _mpi / _compact_vox), differentiable in the density grid through
     `weights`, `alphainv_last` and the raw `density` output -- the backward is TrainSample's, inherited (ugrid_train_sample_backward
     + the lookup's scatter).
 
     forward(grid [1,1,X,Y,Z], rays_o [R,3], rays_d [R,3], t [S] or None, xyz_min, xyz_max, mask [mi,mj,mk] bool, cfg) ->
         pts [M2,3], density [M2], alpha [M2], weights [M2], alphainv_last [R], ray_id [M2] i64, step_id [M2] i64, t [M2]
-        (dvgo: float(step_id)), inner [M2] bool (dvgo: all True)
+        (dvgo, mpi: float(step_id)), inner [M2] bool (dvgo, mpi: all True)
     cfg (host values): mode, act_shift, interval, thres, mask_scale[3], mask_shift[3] and
-        dcvgo: scene_center[3], scene_radius[3], bg_len, norm_l2, dist_thres;   dvgo: near, far, stepdist, slots"""
+        dcvgo: scene_center[3], scene_radius[3], bg_len, norm_l2, dist_thres;   dvgo: near, far, stepdist, slots;
+        mpi: n_steps, mpi_depth and act_shift = the DEVICE tensor of the per-plane shift ([mpi_depth] values: it is part of the
+             density the march stores -- the returned `density` is grid + shift -- and Raw2Alpha's own shift is 0)"""
 
     @staticmethod
     def forward(ctx, grid, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg):
@@ -254,13 +256,20 @@ class TrainSampleVox(TrainSample):
             S = t.numel()
         elif mode == 'dvgo':
             S = int(cfg['slots'])
+        elif mode == 'mpi':
+            S, D = int(cfg['n_steps']), int(cfg['mpi_depth'])
+            tab = cfg['act_shift']
+            _lib.require_cuda(("act_shift", tab))
+            _lib.require_f32(("act_shift", tab))
+            if S < 2 or not 1 <= D <= 256 or tab.numel() != D or not tab.is_contiguous() or tab.device != grid.device:
+                raise RuntimeError("mpi: n_steps >= 2, 1 <= mpi_depth <= 256 and a contiguous act_shift of mpi_depth values on the grid's device")
         else:
             raise ValueError(mode)
         f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
         md = (ctypes.c_int32 * 3)(*[int(x) for x in mask.shape])
         ms, mh = f3(cfg['mask_scale']), f3(cfg['mask_shift'])
         vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        consts = (float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres']))
+        consts = (0.0 if mode == 'mpi' else float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres']))
         if mode == 'dcvgo':
             c3, r3 = f3(cfg['scene_center']), f3(cfg['scene_radius'])
 
@@ -269,6 +278,11 @@ class TrainSampleVox(TrainSample):
                     _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, _lib.ptr(t), S, vp(c3), vp(r3), _lib.ptr(xyz_min),
                     _lib.ptr(xyz_max), float(cfg['bg_len']), int(bool(cfg['norm_l2'])), float(cfg['dist_thres']), _lib.ptr(mask), vp(md),
                     vp(ms), vp(mh), *consts, *outs), "train_sample_dcvgo")
+        elif mode == 'mpi':
+            def march(*outs):
+                _lib.check(_L.ugrid_train_sample_mpi(
+                    _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max), _lib.ptr(tab), D,
+                    _lib.ptr(mask), vp(md), vp(ms), vp(mh), consts[1], consts[2], *outs), "train_sample_mpi")
         else:
             def march(*outs):
                 _lib.check(_L.ugrid_train_sample_dvgo(

@@ -32,6 +32,14 @@ from . import _gradpool
 from ._lib import wait_pending as _lib_wait
 
 
+def _tv_w3(w):
+    """a tv_terms weight as (wx, wy, wz): one number for all axes, or the model's per-axis triple (TrainModel.tv_axis_weights)"""
+    if isinstance(w, (tuple, list)):
+        wx, wy, wz = (float(x) for x in w)
+        return wx, wy, wz
+    return w, w, w
+
+
 def _low_priority_stream():
     """the side stream of step(overlap=...): the lowest priority the device offers (torch maps an out-of-range value to
     the nearest valid one), so that the caller's stream -- the next forward's latency-bound kernels -- is served first
@@ -186,6 +194,7 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
         on the HIP ops: ONE fused pass (adam_upd_cuda.tv_adam_dense -- 7 instead of 13 array transfers, the gradient is
         not written back, bit-identical results); the new parameter values land in a second buffer that is swapped in."""
         w, dense, tv_module = tv
+        w3 = _tv_w3(w)
         fused_fn = getattr(self.ops, 'tv_adam_dense', None)
         if dense and fused_fn is not None and tv_module is None and not use_perlr and param.dim() >= 3 and g.stride() == param.stride():
             alt = self._alt.get(param)
@@ -197,7 +206,7 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
             kw = {'rezero_grad': True} if recycle else {}
             if recycle and touch is not None:
                 kw['touch'] = touch
-            args = (param.data, alt, g, state['exp_avg'], state['exp_avg_sq'], w, w, w, state['step'], beta1, beta2,
+            args = (param.data, alt, g, state['exp_avg'], state['exp_avg_sq'], *w3, state['step'], beta1, beta2,
                     group['lr'], group['eps'], group['skip_zero_grad'])
             if side is not None:
                 # the 7-pass update of this grid on a second HIP stream: the caller's stream goes on (the next forward's
@@ -230,9 +239,9 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
 
         def run():
             if touch is not None and ours and not dense and g.dim() == 5 and g.shape[1] % 4 == 0:
-                tv_module.total_variation_add_grad_touched(param, g, w, w, w, touch)
+                tv_module.total_variation_add_grad_touched(param, g, *w3, touch)
             else:
-                tv_module.total_variation_add_grad(param, g, w, w, w, dense)
+                tv_module.total_variation_add_grad(param, g, *w3, dense)
             self._update(group, param, g, state['exp_avg'], state['exp_avg_sq'], state['step'],
                          self.per_lr if use_perlr else None, recycle=param, touch=touch)
         if side is not None and ours and touch is not None and not dense:
@@ -288,7 +297,7 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
     def step(self, grad_hook=None, tv_terms=None, overlap=None):
         """grad_hook(param, grad): optional in-place edit of the REDUCED gradient before the update.  For a sharded
         parameter the hook receives a full-shape gradient that is zero outside this rank's range.
-        tv_terms: optional {param: (w, dense_mode, tv_module or None)} -- the total-variation term of the training
+        tv_terms: optional {param: (w or (wx, wy, wz), dense_mode, tv_module or None)} -- the total-variation term of the training
         iteration (run_train.py:281-287), applied to the gradient summed over all ranks (a rank-local masked TV would
         give a voxel touched by k of N ranks only k/N of the term); for a replicated parameter in dense mode it is
         fused with the update (see _tv_then_update).
@@ -399,7 +408,7 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
                         w, dense, tv_module = tv_terms[param]
                         if tv_module is None:
                             from . import total_variation_cuda as tv_module
-                        tv_module.total_variation_add_grad(param, full, w, w, w, dense)
+                        tv_module.total_variation_add_grad(param, full, *_tv_w3(w), dense)
                     g_shard[: e - b] = full_g[b:e]
                     del full_g, full
                 if exact:

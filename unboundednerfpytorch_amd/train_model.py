@@ -69,6 +69,13 @@ class TrainModel(nn.Module):
         w = weight * self.world_size_rgb.max() / 128
         self.k0.total_variation_add_grad(w, w, w, dense_mode)
 
+    def tv_axis_weights(self, weight, which='density'):
+        """(wx, wy, wz) of a total-variation weight for the `which` ('density' / 'k0') grid: the model's own scaling of run_train.py's
+        weight / batch size.  Here one number for all axes, world_size.max() / 128 (the two methods above); mpi_model.DirectMPIGO scales
+        z by its plane count.  train_step.train_iteration hands the triple to the optimizer's TV pass."""
+        w = float(weight * (self.world_size_density if which == 'density' else self.world_size_rgb).max() / 128)
+        return (w, w, w)
+
     def _rebuild_mask_cache(self):
         """the mask half of the coarse-to-fine step (dvgo.py:227-234, dcvgo.py:167-174, FourierGrid_model.py:430-437): the cache
         rebuilt at the new density resolution from the old cache and the 3x3x3 max-pooled alpha (of level 0)"""
@@ -188,11 +195,11 @@ class TrainModel(nn.Module):
             return self._logits(k0[:, 3:].contiguous(), viewdirs, ray_id) + k0[:, :3]
         return self._logits(k0, viewdirs, ray_id)
 
-    def _render_loss(self, fused_loss, logits, weights, alphainv_last, density, ray_id, tt, bg):
+    def _render_loss(self, fused_loss, logits, weights, alphainv_last, density, ray_id, tt, bg, s=None):
         """Training tail as ONE op (ops.RenderLoss): sigmoid, compositing, background and the loss terms of run_train.py:254-279.
         train_step.train_iteration passes fused_loss = {'target': [N,3], 'coef': ops.loss_coefficients(...)}.
-        -> loss, mse, rgb_marched"""
-        return _ops.RenderLoss.apply(logits.contiguous(), weights, alphainv_last, density, ray_id, tt, None, fused_loss['target'], bg,
+        s: the samples' normalised distances where they are not 1 - 1 / (1 + t) (DirectMPIGO).  -> loss, mse, rgb_marched"""
+        return _ops.RenderLoss.apply(logits.contiguous(), weights, alphainv_last, density, ray_id, tt, s, fused_loss['target'], bg,
                                      fused_loss['coef'])
 
     def _composed_tail(self, N, rgb, alpha, weights, alphainv_last, ray_id, step_id, bg, render_depth, contracted=None):

@@ -10,7 +10,8 @@ Same functions, same return tuples and the same random streams here (numpy permu
 the 'random' mode), with the rays produced by the one-kernel `fourier_render.get_rays_of_a_view` when the poses live on the
 GPU.  On an MI355X the natural set-up is `load2gpu_on_the_fly = False`: 250 full-HD views are 500 M rays x 48 B = 25 GB of
 the 288 GB, so the ray table stays resident and a batch is four device-side row gathers -- no per-iteration H2D copy.
-NDC rays belong to the DirectMPIGO path (out of scope).
+NDC (forward-facing) ray tables -- cfg.data.ndc, the DirectMPIGO path (mpi_model.py) -- come from the functions of their own,
+`get_training_rays_ndc` / `get_training_rays_flatten_ndc`; the four functions above refuse ndc=True.
 
 Also the two ray-preparation utilities the models and DirectVoxGORenderer share, `voxel_count_views` and `hit_coarse_geo`."""
 import numpy as np
@@ -21,13 +22,19 @@ from .fourier_render import get_rays_of_a_view
 FOURIERGRID_DATASETS = ("waymo", "mega", "nerfpp")      # FourierGrid_model.py:307
 
 
+_NDC = object()
+
+
 def _rays(H, W, K, c2w, ndc, inverse_y, flip_x, flip_y, device):
-    if ndc:
-        raise NotImplementedError("NDC rays belong to the DirectMPIGO path (out of scope, SURVEY.md section 2)")
+    if ndc is _NDC:                  # (only the NDC functions below pass it; a caller's ndc=True is refused)
+        ndc = True
+    elif ndc:
+        raise NotImplementedError("NDC ray tables are built by get_training_rays_ndc / get_training_rays_flatten_ndc "
+                                  "(the DirectMPIGO path, mpi_model.py)")
     c2w = torch.as_tensor(c2w, dtype=torch.float32)
     if device.type == "cuda":
-        c2w = c2w.to(device)         # device-resident pose: ONE kernel per view (ugrid_rays_of_a_view)
-    o, d, v = get_rays_of_a_view(int(H), int(W), K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y)
+        c2w = c2w.to(device)         # device-resident pose: ONE kernel per view (ugrid_rays_of_a_view / _ndc)
+    o, d, v = get_rays_of_a_view(int(H), int(W), K, c2w, inverse_y=inverse_y, flip_x=flip_x, flip_y=flip_y, ndc=bool(ndc))
     return o.to(device), d.to(device), v.to(device)
 
 
@@ -79,6 +86,20 @@ def _flatten(rgb_tr_ori, train_poses, HW, Ks, ndc, inverse_y, flip_x, flip_y, wi
 def get_training_rays_flatten(rgb_tr_ori, train_poses, HW, Ks, ndc, inverse_y, flip_x, flip_y):
     """dvgo.get_training_rays_flatten (dvgo.py:594-616): views of any size, all pixels, flattened to [N,3]."""
     rgb, o, d, v, _, imsz = _flatten(rgb_tr_ori, train_poses, HW, Ks, ndc, inverse_y, flip_x, flip_y, False)
+    return rgb, o, d, v, imsz
+
+
+@torch.no_grad()
+def get_training_rays_ndc(rgb_tr, train_poses, HW, Ks, inverse_y, flip_x, flip_y):
+    """dvgo.get_training_rays(ndc=True) (dvgo.py:562-590): rays_o / rays_d in the forward-facing NDC space (ndc_rays with near = 1),
+    viewdirs the world directions -- the ray table of DirectMPIGO's 'random' sampler (configs/llff)."""
+    return get_training_rays(rgb_tr, train_poses, HW, Ks, _NDC, inverse_y, flip_x, flip_y)
+
+
+@torch.no_grad()
+def get_training_rays_flatten_ndc(rgb_tr_ori, train_poses, HW, Ks, inverse_y, flip_x, flip_y):
+    """dvgo.get_training_rays_flatten(ndc=True) (dvgo.py:594-616)"""
+    rgb, o, d, v, _, imsz = _flatten(rgb_tr_ori, train_poses, HW, Ks, _NDC, inverse_y, flip_x, flip_y, False)
     return rgb, o, d, v, imsz
 
 

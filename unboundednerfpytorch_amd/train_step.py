@@ -31,6 +31,11 @@ def maybe_scale_grids(model, optimizer, cfg_train, cfg_model, global_step, **opt
     if hasattr(model, 'num_voxels_density'):
         model.scale_volume_grid(int(_get(cfg_model, 'num_voxels_density') / (2 ** rest)),
                                 int(_get(cfg_model, 'num_voxels_rgb') / (2 ** rest)))
+    elif hasattr(model, 'mpi_depth'):      # mpi_model.DirectMPIGO (run_train.py:190-192): the plane count stays
+        nv = _get(cfg_model, 'num_voxels', None)
+        if nv is None:
+            nv = _get(cfg_model, 'num_voxels_rgb')
+        model.scale_volume_grid(int(nv / (2 ** rest)), model.mpi_depth)
     else:       # voxgo_model.DirectVoxGO / DirectContractedVoxGO: one resolution for both grids.  The reference's configs carry it
         # as `num_voxels_rgb` (run_train.py:190-194 scales these models with cur_voxels_rgb); a plain `num_voxels` is accepted too
         nv = _get(cfg_model, 'num_voxels', None)
@@ -123,15 +128,19 @@ def train_iteration(model, optimizer, rays_o, rays_d, viewdirs, target, cfg_trai
         # run_train.py:281-287.  The TV term is applied to the gradient the optimizer is about to use -- inside
         # optimizer.step, i.e. AFTER the cross-rank reduction in data-parallel runs (in a single process that is exactly
         # "TV, then step", and in dense mode the HIP optimizer fuses the two passes).  weight / batch size, then the
-        # models' own scaling by world_size.max() / 128.
+        # models' own scaling (TrainModel.tv_axis_weights: world_size.max() / 128 on every axis; DirectMPIGO: per axis).
         dense = global_step < _get(cfg_train, 'tv_dense_before', 0)
         n_global = n_rays * world_size
         tv_terms = {}
+
+        def tv_weight(base, which, ws):      # a float, or (wx, wy, wz) from the model's hook
+            hook_ = getattr(model, 'tv_axis_weights', None)
+            return hook_(base, which) if hook_ is not None else float(base * ws.max() / 128)
         if _get(cfg_train, 'weight_tv_density', 0.0) > 0:
-            tv_terms[model.density.grid] = (float(_get(cfg_train, 'weight_tv_density') / n_global * model.world_size_density.max() / 128),
+            tv_terms[model.density.grid] = (tv_weight(_get(cfg_train, 'weight_tv_density') / n_global, 'density', model.world_size_density),
                                             dense, model.density.tv_module)
         if _get(cfg_train, 'weight_tv_k0', 0.0) > 0:
-            tv_terms[model.k0.grid] = (float(_get(cfg_train, 'weight_tv_k0') / n_global * model.world_size_rgb.max() / 128),
+            tv_terms[model.k0.grid] = (tv_weight(_get(cfg_train, 'weight_tv_k0') / n_global, 'k0', model.world_size_rgb),
                                        dense, model.k0.tv_module)
     overlap = bool(tv_terms and overlap_k0_update and world_size == 1 and model.k0.grid in tv_terms)
     hook = None
