@@ -682,3 +682,66 @@ def test_slab_ordered_dense_tv_adam_is_bit_identical(shape, skip_zero):
     (ad.masked_adam_upd if skip_zero else ad.adam_upd)(pr, gr2, mr, vr, *args)
     assert torch.equal(outs[3][0], pr) and torch.equal(outs[3][1], mr) and torch.equal(outs[3][2], vr)
     assert not torch.equal(pr, p0)
+
+
+@pytest.mark.parametrize("shape", [(3, 4, 9, 10, 28), (2, 4, 5, 7, 12)])
+def test_tv_block_orders_and_entry_points_agree_with_the_oracle(shape):
+    """Every TV / fused TV + Adam entry point under every workgroup order (ugrid_tune tv_xcd = 0 linear, 1 XCD-contiguous,
+    2 + non-temporal streams, 3 + slab order where the planes are large -- not here) against the CPU oracle, bit for bit (pure
+    IEEE add / mul / div / sqrt on both sides: no tolerance), with three DIFFERENT axis weights and a gradient of ~60 % exact zeros.
+    (3, 4, 9, 10, 28): 30 240 elements = 30 workgroups = 3 x 8 + 6, so the XCD renumbering has a remainder; (2, 4, 5, 7, 12): 4
+    workgroups, fewer than the 8 XCDs.  sz_k % 4 == 0 and C % 4 == 0: every float4 kernel applies, in both layouts."""
+    from unboundednerfpytorch_amd import _lib, adam_upd_cuda as ad, total_variation_cuda as tv
+    from unboundednerfpytorch_amd.fourier_render import tune
+    n = int(np.prod(shape))
+    w3, args = (0.3, 0.2, 0.1), (5, 0.9, 0.99, 0.1, 1e-8)
+    p = torch.from_numpy(synth.normal(90, n, 0.0, 2.0).reshape(shape))
+    g = synth.normal(91, n).reshape(shape)
+    g[np.abs(g) < 0.35] = 0                                    # scattered zeros, and 45 % of the (x, y) rows zero in all channels:
+    P, C, X, Y, Z = shape                                      # some 256-byte lines of the channel-last storage hold nothing
+    g *= (synth.uniform(94, P * X * Y, 0.0, 1.0) >= 0.45).reshape(P, 1, X, Y, 1)
+    g = torch.from_numpy(g.astype(np.float32))
+    assert 0.5 < float((g == 0).float().mean()) < 0.7
+    m = torch.from_numpy(synth.normal(92, n, 0, 0.1).reshape(shape))
+    v = torch.from_numpy(synth.uniform(93, n, 0, 0.01).reshape(shape))
+    # the oracle, once: the TV gradient dense / masked, and the dense one followed by (masked_)adam_upd
+    tv_ref, fused_ref = {}, {}
+    for dense in (True, False):
+        tv_ref[dense] = g.clone()
+        ref_ops.total_variation_add_grad(p, tv_ref[dense], *w3, dense)
+    for skip in (True, False):
+        fused_ref[skip] = [p.clone(), m.clone(), v.clone()]
+        (ref_ops.masked_adam_upd if skip else ref_ops.adam_upd)(fused_ref[skip][0], tv_ref[True], *fused_ref[skip][1:], *args)
+    layouts = {"canonical": lambda t: t.cuda(), "channel-last": lambda t: t.cuda().contiguous(memory_format=torch.channels_last_3d)}
+    # touched-line bitmaps of the channel-last gradient: 64 floats of the flat storage per line, bit (line & 31) of word (line >> 5)
+    n_words = int(_lib.load().ugrid_touch_words(n))
+    flat = g.permute(0, 2, 3, 4, 1).reshape(-1).numpy()
+    marked = np.zeros(n_words * 32, dtype=bool)
+    for line in range((n + 63) // 64):
+        marked[line] = bool(np.any(flat[line * 64:(line + 1) * 64] != 0))
+    assert 0 < int(marked.sum()) < (n + 63) // 64
+    pack = lambda bits: torch.from_numpy((bits.reshape(-1, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1)
+                                         .astype(np.uint32).view(np.int32)).cuda()
+    bitmaps = {"every line": pack(np.ones(n_words * 32, dtype=bool)), "the non-zero lines": pack(marked)}
+    try:
+        for xcd in (0, 1, 2, 3):
+            tune("tv_xcd", xcd)
+            for name, put in layouts.items():
+                what = "tv_xcd %d, %s" % (xcd, name)
+                pd = put(p)
+                for dense in (True, False):
+                    gd = put(g)
+                    tv.total_variation_add_grad(pd, gd, *w3, dense)
+                    assert torch.equal(gd.cpu(), tv_ref[dense]), (what, "TV", dense)
+                fused = [(skip, None, "") for skip in (True, False)]
+                if name == "channel-last":
+                    fused += [(skip, bm, which) for skip in (True, False) for which, bm in bitmaps.items()]
+                for skip, bm, which in fused:
+                    gd, md, vd, out = put(g), put(m), put(v), torch.empty_like(pd, memory_format=torch.preserve_format)
+                    kw = {} if bm is None else {"touch": bm.clone()}
+                    assert ad.tv_adam_dense(pd, out, gd, md, vd, *w3, *args, skip, **kw), (what, skip, which)
+                    for got, ref, part in zip((out, md, vd), fused_ref[skip], ("param", "exp_avg", "exp_avg_sq")):
+                        assert torch.equal(got.cpu(), ref), (what, "fused", skip, which, part)
+                    assert torch.equal(gd.cpu(), g) and torch.equal(pd.cpu(), p), (what, "inputs changed")
+    finally:
+        tune("tv_xcd", 3)

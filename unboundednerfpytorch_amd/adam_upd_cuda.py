@@ -83,30 +83,16 @@ def tv_adam_dense(param, param_out, grad, exp_avg, exp_avg_sq, wx, wy, wz, step,
     _lib.require_f32(*named)
     sz_i, sz_j, sz_k = param.shape[-3:]
     flags = int(bool(skip_zero_grad)) | (2 if rezero_grad else 0)
-    if cl and touch is not None:       # gradient lines the backward did not mark are known zeros: not read
-        with _lib.guard(param.device):
-            rc = _L.ugrid_tv_adam_dense_cl_touch(_lib.ptr(param), _lib.ptr(param_out), _lib.ptr(grad), _lib.ptr(exp_avg),
-                                                 _lib.ptr(exp_avg_sq), float(wx), float(wy), float(wz), sz_i, sz_j, sz_k, param.shape[1],
-                                                 param.numel(), int(step), float(beta1), float(beta2), float(lr), float(eps), flags,
-                                                 _lib.ptr(touch), _lib.stream_of(param))
-        if rc == 801:
-            return False
-        _lib.check(rc, "tv_adam_dense (touch)")
-        return True
+    fn, what, dims, extra = _L.ugrid_tv_adam_dense, "tv_adam_dense", (sz_i, sz_j, sz_k), ()
     if cl:
-        with _lib.guard(param.device):
-            rc = _L.ugrid_tv_adam_dense_cl(_lib.ptr(param), _lib.ptr(param_out), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                           float(wx), float(wy), float(wz), sz_i, sz_j, sz_k, param.shape[1], param.numel(), int(step),
-                                           float(beta1), float(beta2), float(lr), float(eps), flags, _lib.stream_of(param))
-        if rc == 801:
-            return False
-        _lib.check(rc, "tv_adam_dense")
-        return True
+        fn, dims = _L.ugrid_tv_adam_dense_cl, dims + (param.shape[1],)
+    if cl and touch is not None:       # gradient lines the backward did not mark are known zeros: not read
+        fn, what, extra = _L.ugrid_tv_adam_dense_cl_touch, "tv_adam_dense (touch)", (_lib.ptr(touch),)
     with _lib.guard(param.device):
-        rc = _L.ugrid_tv_adam_dense(_lib.ptr(param), _lib.ptr(param_out), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
-                                    float(wx), float(wy), float(wz), sz_i, sz_j, sz_k, param.numel(), int(step), float(beta1),
-                                    float(beta2), float(lr), float(eps), flags, _lib.stream_of(param))
+        rc = fn(_lib.ptr(param), _lib.ptr(param_out), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), float(wx), float(wy),
+                float(wz), *dims, param.numel(), int(step), float(beta1), float(beta2), float(lr), float(eps), flags, *extra,
+                _lib.stream_of(param))
     if rc == 801:      # hipErrorNotSupported
         return False
-    _lib.check(rc, "tv_adam_dense")
+    _lib.check(rc, what)
     return True

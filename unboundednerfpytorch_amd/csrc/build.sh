@@ -6,10 +6,12 @@ cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include"
 O=${UG_OBJ:-../../build/obj}      # UG_OBJ: separate object directory (parallel A/B builds)
 mkdir -p $O
-rm -f $O/ugrid_ops.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o   # a failed compile must not link a stale object
-OBJS="$O/ugrid_ops.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o"
+rm -f $O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o   # a failed compile must not link a stale object
+OBJS="$O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o"
 pids=()
 hipcc $FLAGS -c ugrid_ops.hip -o $O/ugrid_ops.o "$@" &
+pids+=($!)
+hipcc $FLAGS -c ugrid_update.hip -o $O/ugrid_update.o "$@" &
 pids+=($!)
 # packed fp32 VALU (v_pk_*_f32 from the SLP vectoriser) issues at half rate on gfx950 and needs extra moves to form
 # register pairs: the VALU-bound march kernel is 16 % faster without it, the shade kernel 1.3 %

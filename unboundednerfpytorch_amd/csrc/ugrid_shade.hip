@@ -4,7 +4,7 @@
 #include "ugrid_shade_pc.h"
 
 extern "C" int ug_set_march_waves(int w);  // ugrid_march.hip
-extern "C" int ug_set_tv_xcd(int m);        // ugrid_ops.hip
+extern "C" int ug_set_tv_xcd(int m);        // ugrid_update.hip
 extern "C" int ug_set_train_mlp(int m);     // ugrid_train_mlp.hip
 #define UG_PC12_NBL 3        // gather items (x 6 dwordx4) in flight per producer wave of the 12-wave geometry (4 spill)
 static int g_shade_pc = 2;   // ugrid_tune("shade_pc", 0|1|2): 2 = 12-wave producer / consumer shade kernel where it applies (default),

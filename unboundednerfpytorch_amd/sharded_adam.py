@@ -189,12 +189,47 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
             return None
         return _gradpool.touch_of(param, g)
 
+    def _ensure_state(self, param, shard=None):
+        """the parameter's optimizer state with `step` advanced by one; created on first use -- moments in the parameter's own
+        shape and layout, or (shard = (b, e, per)) for this rank's flat range of `per` elements only"""
+        state = self.state[param]
+        if len(state) == 0:
+            state['step'] = 0
+            for k in ('exp_avg', 'exp_avg_sq'):
+                if shard is None:
+                    state[k] = torch.zeros_like(param, memory_format=torch.preserve_format)
+                else:
+                    state[k] = torch.zeros(shard[2], dtype=param.dtype, device=param.device)
+            if shard is not None:
+                state['shard'] = shard
+        state['step'] += 1
+        return state
+
+    @staticmethod
+    def _on_side_stream(side, param, arrays, fn):
+        """fn() queued on the second HIP stream: the caller's stream goes on (the next forward's density march, its host syncs, the
+        launch-bound glue) and meets the work at _lib.wait_pending(param) -- param._ug_pending, set when fn() returns true"""
+        side.wait_stream(torch.cuda.current_stream(param.device))
+        # every array the side-stream kernels touch was allocated on the caller's stream: tell the caching allocator,
+        # so that a buffer whose last reference dies before the pass has run (zero_grad(set_to_none), a pool that
+        # refuses it, a replaced `alt`) is not handed to another tensor while it is still in use
+        for t_ in arrays:
+            t_.record_stream(side)
+        with torch.cuda.stream(side):
+            done = fn()
+            if done:
+                ev = torch.cuda.Event()
+                ev.record(side)
+                param._ug_pending = ev
+        return done
+
     def _tv_then_update(self, group, param, g, state, tv, use_perlr, side=None, touch=None):
         """Total-variation term (w, dense_mode, tv_module) on the reduced gradient `g`, then the Adam update.  Dense mode
         on the HIP ops: ONE fused pass (adam_upd_cuda.tv_adam_dense -- 7 instead of 13 array transfers, the gradient is
         not written back, bit-identical results); the new parameter values land in a second buffer that is swapped in."""
         w, dense, tv_module = tv
         w3 = _tv_w3(w)
+        moments = (state['exp_avg'], state['exp_avg_sq'])
         fused_fn = getattr(self.ops, 'tv_adam_dense', None)
         if dense and fused_fn is not None and tv_module is None and not use_perlr and param.dim() >= 3 and g.stride() == param.stride():
             alt = self._alt.get(param)
@@ -206,25 +241,14 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
             kw = {'rezero_grad': True} if recycle else {}
             if recycle and touch is not None:
                 kw['touch'] = touch
-            args = (param.data, alt, g, state['exp_avg'], state['exp_avg_sq'], *w3, state['step'], beta1, beta2,
-                    group['lr'], group['eps'], group['skip_zero_grad'])
-            if side is not None:
-                # the 7-pass update of this grid on a second HIP stream: the caller's stream goes on (the next forward's
-                # density march, its host syncs, the launch-bound glue) and meets it again at _lib.wait_pending
-                side.wait_stream(torch.cuda.current_stream(param.device))
-                # every array the side-stream kernel touches was allocated on the caller's stream: tell the caching
-                # allocator, so that a buffer whose last reference dies before the pass has run (zero_grad(set_to_none),
-                # a pool that refuses it, a replaced `alt`) is not handed to another tensor while it is still in use
-                for t_ in (g, alt, param.data, state['exp_avg'], state['exp_avg_sq']) + ((touch,) if 'touch' in kw else ()):
-                    t_.record_stream(side)
-                with torch.cuda.stream(side):
-                    done = fused_fn(*args, **kw)
-                    if done:
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                        param._ug_pending = ev
+
+            def fused():
+                return fused_fn(param.data, alt, g, *moments, *w3, state['step'], beta1, beta2, group['lr'], group['eps'],
+                                group['skip_zero_grad'], **kw)
+            if side is not None:      # the 7-pass update of this grid on the second stream
+                done = self._on_side_stream(side, param, (g, alt, param.data, *moments) + ((touch,) if 'touch' in kw else ()), fused)
             else:
-                done = fused_fn(*args, **kw)
+                done = fused()
             if done:
                 self._alt[param] = param.data
                 param.data = alt
@@ -242,21 +266,35 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
                 tv_module.total_variation_add_grad_touched(param, g, *w3, touch)
             else:
                 tv_module.total_variation_add_grad(param, g, *w3, dense)
-            self._update(group, param, g, state['exp_avg'], state['exp_avg_sq'], state['step'],
-                         self.per_lr if use_perlr else None, recycle=param, touch=touch)
+            self._update(group, param, g, *moments, state['step'], self.per_lr if use_perlr else None, recycle=param, touch=touch)
+            return True
         if side is not None and ours and touch is not None and not dense:
-            # masked TV + masked Adam on the marked lines, queued on the second stream like the dense pass (they update the
-            # parameter in place: consumers meet them at _lib.wait_pending)
-            side.wait_stream(torch.cuda.current_stream(param.device))
-            for t_ in (g, param.data, state['exp_avg'], state['exp_avg_sq'], touch):
-                t_.record_stream(side)
-            with torch.cuda.stream(side):
-                run()
-                ev = torch.cuda.Event()
-                ev.record(side)
-                param._ug_pending = ev
+            # masked TV + masked Adam on the marked lines (in place), queued on the second stream like the dense pass
+            self._on_side_stream(side, param, (g, param.data, *moments, touch), run)
         else:
             run()
+
+    def _side_stream(self):
+        self._side = getattr(self, '_side', None) or _low_priority_stream()
+        return self._side
+
+    def _step_replicated(self, group, param, world=1, scale=None, grad_hook=None, tv_term=None, side=None):
+        """replicated: every rank applies the same (summed) gradient to its own full state"""
+        g = param.grad
+        if world > 1:
+            dist.all_reduce(g, group=self.group)
+            if scale is not None:
+                g.mul_(scale)
+        if grad_hook is not None:
+            grad_hook(param, g)
+        state = self._ensure_state(param)
+        use_perlr = self.per_lr is not None and param.shape == self.per_lr.shape
+        touch = self._touch_of(param, g, grad_hook)
+        if tv_term is not None:
+            self._tv_then_update(group, param, g, state, tv_term, use_perlr, side, touch=touch)
+        else:
+            self._update(group, param, g, state['exp_avg'], state['exp_avg_sq'], state['step'],
+                         self.per_lr if use_perlr else None, recycle=param, touch=touch)
 
     @torch.no_grad()
     def step_param(self, param, tv_term=None, overlap=False):
@@ -270,28 +308,21 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
         if group is None:
             return False
         _lib_wait(param)
-        state = self.state[param]
-        g = param.grad
-        if len(state) == 0:
-            state['step'] = 0
-            state['exp_avg'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-            state['exp_avg_sq'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-        state['step'] += 1
-        use_perlr = self.per_lr is not None and param.shape == self.per_lr.shape
-        touch = self._touch_of(param, g, None)
-        if tv_term is not None:
-            side = None
-            if overlap:
-                side = self._side = getattr(self, '_side', None) or _low_priority_stream()
-            self._tv_then_update(group, param, g, state, tv_term, use_perlr, side, touch=touch)
-        else:
-            self._update(group, param, g, state['exp_avg'], state['exp_avg_sq'], state['step'],
-                         self.per_lr if use_perlr else None, recycle=param, touch=touch)
+        self._step_replicated(group, param, tv_term=tv_term, side=self._side_stream() if (overlap and tv_term is not None) else None)
         # remembered by OBJECT (a weak reference beside the id): a parameter that is replaced -- scale_volume_grid makes new
         # ones -- may get the id of a dead one, and must not be skipped by the next step() on the strength of that
         self._early = getattr(self, '_early', None) or {}
         self._early[id(param)] = weakref.ref(param)
         return True
+
+    def _multi_eligible(self, param, world, tv_terms, grad_hook):
+        """a small plain tensor (the rgbnet's) whose update can share ONE launch with its group's others (adam_upd_multi):
+        single process, HIP ops, nothing that needs the parameter on its own (TV term, per-voxel lr, gradient hook)"""
+        use_perlr = self.per_lr is not None and param.shape == self.per_lr.shape
+        return (getattr(self.ops, 'adam_upd_multi', None) is not None and world == 1 and param.numel() <= self.MULTI_MAX_NUMEL
+                and param not in tv_terms and not use_perlr and grad_hook is None and param.is_cuda and param.is_contiguous()
+                and param.grad.is_contiguous() and param.dtype == torch.float32 and param.grad.dtype == torch.float32
+                and param.dim() != 5 and param.grad.device == param.device)
 
     @torch.no_grad()
     def step(self, grad_hook=None, tv_terms=None, overlap=None):
@@ -310,11 +341,8 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
         tv_terms = tv_terms or {}
         self.last_exchange = {}          # (per step: parameters are replaced at every pg_scale event)
         scale = (1.0 / world) if (self.average and world > 1) else None
-        side = None
-        if overlap and world == 1:
-            side = self._side = getattr(self, '_side', None) or _low_priority_stream()
+        side = self._side_stream() if (overlap and world == 1) else None
         early, self._early = (getattr(self, '_early', None) or {}), {}
-        multi = getattr(self.ops, 'adam_upd_multi', None)
         for group in self.param_groups:
             batch = []        # small tensors of this group, updated by ONE launch at the end of the group (HIP ops only)
             for param in group['params']:
@@ -322,122 +350,93 @@ class ShardedMaskedAdam(torch.optim.Optimizer):
                 if param.grad is None or (ref is not None and ref() is param):   # (updated already by step_param during the backward)
                     continue
                 _lib_wait(param)
-                state = self.state[param]
-                n = param.numel()
-                use_perlr = self.per_lr is not None and param.shape == self.per_lr.shape
-                sharded = world > 1 and n >= self.min_shard_numel
-                if (multi is not None and world == 1 and n <= self.MULTI_MAX_NUMEL and param not in tv_terms and not use_perlr
-                        and grad_hook is None and param.is_cuda and param.is_contiguous() and param.grad.is_contiguous()
-                        and param.dtype == torch.float32 and param.grad.dtype == torch.float32 and param.dim() != 5
-                        and param.grad.device == param.device):
-                    if len(state) == 0:
-                        state['step'] = 0
-                        state['exp_avg'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-                        state['exp_avg_sq'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-                    state['step'] += 1
+                if self._multi_eligible(param, world, tv_terms, grad_hook):
+                    state = self._ensure_state(param)
                     batch.append((param.data, param.grad, state['exp_avg'], state['exp_avg_sq'], state['step'], group['lr']))
-                    continue
-                if not sharded:
-                    # replicated: every rank applies the same (summed) gradient to its own full state
-                    g = param.grad
-                    if world > 1:
-                        dist.all_reduce(g, group=self.group)
-                        if scale is not None:
-                            g.mul_(scale)
-                    if grad_hook is not None:
-                        grad_hook(param, g)
-                    if len(state) == 0:
-                        state['step'] = 0
-                        state['exp_avg'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-                        state['exp_avg_sq'] = torch.zeros_like(param, memory_format=torch.preserve_format)
-                    state['step'] += 1
-                    touch = self._touch_of(param, g, grad_hook)
-                    if param in tv_terms:
-                        self._tv_then_update(group, param, g, state, tv_terms[param], use_perlr,
-                                             side if (side is not None and any(param is q for q in overlap)) else None, touch=touch)
-                    else:
-                        self._update(group, param, g, state['exp_avg'], state['exp_avg_sq'], state['step'],
-                                     self.per_lr if use_perlr else None, recycle=param, touch=touch)
-                    continue
-                per = self._shard_len(n, world)
-                total = per * world
-                b = min(n, rank * per)
-                e = min(n, b + per)
-                if len(state) == 0:
-                    state['step'] = 0
-                    state['exp_avg'] = torch.zeros(per, dtype=param.dtype, device=param.device)      # this rank's
-                    state['exp_avg_sq'] = torch.zeros(per, dtype=param.dtype, device=param.device)   # range only
-                    state['shard'] = (b, e, per)
-                state['step'] += 1
-                flat_p = self._flat(param.data)
-                g_full = param.grad
-                if g_full.stride() != param.stride():                    # bring a foreign-layout gradient to the parameter's
-                    g_full = torch.empty_like(param.data).copy_(g_full)
-                flat_g = self._flat(g_full)
-                exact = (total == n)       # no padding: collectives run on the parameter / gradient storage itself
-                if not exact:
-                    pad_g = torch.zeros(total, dtype=flat_g.dtype, device=flat_g.device)
-                    pad_g[:n] = flat_g
-                    flat_g = pad_g
-                # masked update: only elements with a non-zero (reduced, TV-augmented) gradient move, all inside marked lines
-                tv_dense = param in tv_terms and bool(tv_terms[param][1])
-                masked = bool(group['skip_zero_grad']) and not use_perlr and not tv_dense and grad_hook is None
-                plan = self._sparse_plan(param, flat_g, n, per, world, rank) if (self.sparse_exchange and exact) else None
-                if plan is not None:
-                    g_shard = self._sparse_reduce_scatter(plan, flat_g, per, world, rank)
-                    self.last_exchange[id(param)] = {
-                        "mode": "sparse reduce-scatter, dense all-gather", "lines_total": n // self.LINE, "lines_union": int(plan["lines"].numel()),
-                        "line_source": getattr(self, "_line_source", None),
-                        "rows_per_rank_padded": plan["M"], "bitmap_bytes": plan["bitmap_bytes"],
-                        "reduce_scatter_bytes": plan["M"] * world * self.LINE * 4, "all_gather_bytes": per * world * 4,
-                        "dense_bytes_each_way": n * 4}
+                elif world > 1 and param.numel() >= self.min_shard_numel:
+                    self._step_sharded(group, param, world, rank, scale, grad_hook, tv_terms.get(param))
                 else:
-                    g_shard = torch.empty(per, dtype=flat_g.dtype, device=flat_g.device)
-                    dist.reduce_scatter_tensor(g_shard, flat_g, group=self.group)
-                    self.last_exchange[id(param)] = {"mode": "dense", "reduce_scatter_bytes": flat_g.numel() * 4,
-                                                     "all_gather_bytes": per * world * 4}
-                if scale is not None:
-                    g_shard.mul_(scale)
-                if grad_hook is not None or param in tv_terms:
-                    full = torch.zeros_like(param.data)                 # the parameter's own layout
-                    full_g = self._flat(full)
-                    full_g[b:e] = g_shard[: e - b]
-                    if grad_hook is not None:
-                        grad_hook(param, full)
-                    if param in tv_terms:
-                        w, dense, tv_module = tv_terms[param]
-                        if tv_module is None:
-                            from . import total_variation_cuda as tv_module
-                        tv_module.total_variation_add_grad(param, full, *_tv_w3(w), dense)
-                    g_shard[: e - b] = full_g[b:e]
-                    del full_g, full
-                if exact:
-                    p_shard = flat_p[b:b + per]                  # a view: updated in place
-                else:
-                    p_shard = torch.zeros(per, dtype=flat_p.dtype, device=flat_p.device)
-                    p_shard[: e - b] = flat_p[b:e]
-                lr_shard = None
-                if use_perlr:
-                    lr_shard = torch.zeros(per, dtype=torch.float32, device=param.device)
-                    lr_shard[: e - b] = self.per_lr.reshape(-1)[b:e]
-                self._update(group, p_shard, g_shard, state['exp_avg'], state['exp_avg_sq'], state['step'], lr_shard)
-                if plan is not None and masked:
-                    self._sparse_all_gather(plan, flat_p, world, rank)
-                    self.last_exchange[id(param)]["all_gather_bytes"] = plan["M"] * world * self.LINE * 4
-                    self.last_exchange[id(param)]["mode"] = "sparse"
-                elif exact:
-                    dist.all_gather_into_tensor(flat_p, p_shard.clone(), group=self.group)
-                else:
-                    full = torch.empty(total, dtype=flat_p.dtype, device=flat_p.device)
-                    dist.all_gather_into_tensor(full, p_shard, group=self.group)
-                    flat_p.copy_(full[:n])
+                    on_side = side is not None and param in tv_terms and any(param is q for q in overlap)
+                    self._step_replicated(group, param, world, scale, grad_hook, tv_terms.get(param), side if on_side else None)
             # one launch per DEVICE: the multi-tensor kernel runs on its first item's device and stream (a group that spans
             # devices must not hand it foreign pointers -- ADVICE r5)
             by_dev = {}
             for item in batch:
                 by_dev.setdefault(item[0].device, []).append(item)
             for items in by_dev.values():
-                multi(items, group['betas'][0], group['betas'][1], group['eps'], bool(group['skip_zero_grad']))
+                self.ops.adam_upd_multi(items, group['betas'][0], group['betas'][1], group['eps'], bool(group['skip_zero_grad']))
+
+    def _step_sharded(self, group, param, world, rank, scale, grad_hook, tv_term):
+        """sharded: reduce-scatter the gradient, update this rank's flat range [b, e) of the parameter, all-gather the ranges"""
+        n = param.numel()
+        use_perlr = self.per_lr is not None and param.shape == self.per_lr.shape
+        per = self._shard_len(n, world)
+        total = per * world
+        b = min(n, rank * per)
+        e = min(n, b + per)
+        state = self._ensure_state(param, (b, e, per))
+        flat_p = self._flat(param.data)
+        g_full = param.grad
+        if g_full.stride() != param.stride():                    # bring a foreign-layout gradient to the parameter's
+            g_full = torch.empty_like(param.data).copy_(g_full)
+        flat_g = self._flat(g_full)
+        exact = (total == n)       # no padding: collectives run on the parameter / gradient storage itself
+        if not exact:
+            pad_g = torch.zeros(total, dtype=flat_g.dtype, device=flat_g.device)
+            pad_g[:n] = flat_g
+            flat_g = pad_g
+        # masked update: only elements with a non-zero (reduced, TV-augmented) gradient move, all inside marked lines
+        tv_dense = tv_term is not None and bool(tv_term[1])
+        masked = bool(group['skip_zero_grad']) and not use_perlr and not tv_dense and grad_hook is None
+        plan = self._sparse_plan(param, flat_g, n, per, world, rank) if (self.sparse_exchange and exact) else None
+        if plan is not None:
+            g_shard = self._sparse_reduce_scatter(plan, flat_g, per, world, rank)
+            self.last_exchange[id(param)] = {
+                "mode": "sparse reduce-scatter, dense all-gather", "lines_total": n // self.LINE, "lines_union": int(plan["lines"].numel()),
+                "line_source": getattr(self, "_line_source", None),
+                "rows_per_rank_padded": plan["M"], "bitmap_bytes": plan["bitmap_bytes"],
+                "reduce_scatter_bytes": plan["M"] * world * self.LINE * 4, "all_gather_bytes": per * world * 4,
+                "dense_bytes_each_way": n * 4}
+        else:
+            g_shard = torch.empty(per, dtype=flat_g.dtype, device=flat_g.device)
+            dist.reduce_scatter_tensor(g_shard, flat_g, group=self.group)
+            self.last_exchange[id(param)] = {"mode": "dense", "reduce_scatter_bytes": flat_g.numel() * 4,
+                                             "all_gather_bytes": per * world * 4}
+        if scale is not None:
+            g_shard.mul_(scale)
+        if grad_hook is not None or tv_term is not None:
+            full = torch.zeros_like(param.data)                 # the parameter's own layout
+            full_g = self._flat(full)
+            full_g[b:e] = g_shard[: e - b]
+            if grad_hook is not None:
+                grad_hook(param, full)
+            if tv_term is not None:
+                w, dense, tv_module = tv_term
+                if tv_module is None:
+                    from . import total_variation_cuda as tv_module
+                tv_module.total_variation_add_grad(param, full, *_tv_w3(w), dense)
+            g_shard[: e - b] = full_g[b:e]
+            del full_g, full
+        if exact:
+            p_shard = flat_p[b:b + per]                  # a view: updated in place
+        else:
+            p_shard = torch.zeros(per, dtype=flat_p.dtype, device=flat_p.device)
+            p_shard[: e - b] = flat_p[b:e]
+        lr_shard = None
+        if use_perlr:
+            lr_shard = torch.zeros(per, dtype=torch.float32, device=param.device)
+            lr_shard[: e - b] = self.per_lr.reshape(-1)[b:e]
+        self._update(group, p_shard, g_shard, state['exp_avg'], state['exp_avg_sq'], state['step'], lr_shard)
+        if plan is not None and masked:
+            self._sparse_all_gather(plan, flat_p, world, rank)
+            self.last_exchange[id(param)]["all_gather_bytes"] = plan["M"] * world * self.LINE * 4
+            self.last_exchange[id(param)]["mode"] = "sparse"
+        elif exact:
+            dist.all_gather_into_tensor(flat_p, p_shard.clone(), group=self.group)
+        else:
+            full = torch.empty(total, dtype=flat_p.dtype, device=flat_p.device)
+            dist.all_gather_into_tensor(full, p_shard, group=self.group)
+            flat_p.copy_(full[:n])
 
     # -- sparse (touched-line) exchange ----------------------------------------------------------------
     def _line_bits(self, param, flat_g, n):

@@ -34,24 +34,15 @@ def _tv(param, grad, wx, wy, wz, dense_mode, touch):
         return
     if touch is not None and (not cl or dense_mode):
         raise RuntimeError("the touched-line bitmap serves the masked mode on channel-last storage only")
-    if cl and touch is not None:
-        with _lib.guard(param.device):
-            rc = _L.ugrid_total_variation_add_grad_cl_touch(_lib.ptr(param), _lib.ptr(grad), float(wx), float(wy), float(wz),
-                                                            param.size(2), param.size(3), param.size(4), param.size(1),
-                                                            param.numel(), _lib.ptr(touch), _lib.stream_of(param))
-        _lib.check(rc, "total_variation_add_grad (touch)")
-        return
-    if cl:      # channel-last storage [P][X][Y][Z][C] of the same logical tensor (training layout, grid.FourierGrid)
-        with _lib.guard(param.device):
-            rc = _L.ugrid_total_variation_add_grad_cl(_lib.ptr(param), _lib.ptr(grad), float(wx), float(wy), float(wz),
-                                                      1 if dense_mode else 0, param.size(2), param.size(3), param.size(4),
-                                                      param.size(1), param.numel(), _lib.stream_of(param))
-        if rc == 801:
-            raise RuntimeError("channel-last total_variation_add_grad needs C % 4 == 0 and fewer than 2^31 elements")
-        _lib.check(rc, "total_variation_add_grad")
-        return
+    # canonical storage, or the channel-last storage [P][X][Y][Z][C] of the same logical tensor (training layout, grid.FourierGrid)
+    fn, what = _L.ugrid_total_variation_add_grad, "total_variation_add_grad"
+    mode, dims, extra = (1 if dense_mode else 0,), (param.size(2), param.size(3), param.size(4)), ()
+    if cl:
+        fn, dims = _L.ugrid_total_variation_add_grad_cl, dims + (param.size(1),)
+    if touch is not None:      # (masked mode only: the entry point takes no dense_mode)
+        fn, what, mode, extra = _L.ugrid_total_variation_add_grad_cl_touch, "total_variation_add_grad (touch)", (), (_lib.ptr(touch),)
     with _lib.guard(param.device):
-        _lib.check(_L.ugrid_total_variation_add_grad(_lib.ptr(param), _lib.ptr(grad), float(wx), float(wy), float(wz),
-                                                     1 if dense_mode else 0, param.size(2), param.size(3),
-                                                     param.size(4), param.numel(), _lib.stream_of(param)),
-                   "total_variation_add_grad")
+        rc = fn(_lib.ptr(param), _lib.ptr(grad), float(wx), float(wy), float(wz), *mode, *dims, param.numel(), *extra, _lib.stream_of(param))
+    if rc == 801 and cl and touch is None:
+        raise RuntimeError("channel-last total_variation_add_grad needs C % 4 == 0 and fewer than 2^31 elements")
+    _lib.check(rc, what)
