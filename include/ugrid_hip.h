@@ -547,7 +547,7 @@ int ugrid_train_sample_compact_vox(int64_t n_rays, int32_t slots_per_ray, float 
  * ~30 Python-issued launches of the op-by-op step (voxgo_model.py; a 1.2 ms step of which 0.8 ms is GPU time).  The calls run
  * the SAME kernels on the SAME sizes in the same order as that step: results are bit-identical to it.
  *
- *   ugrid_voxgo_step_sample    ugrid_train_sample_dvgo / _dcvgo / ugrid_train_sample, the prefix sums of the two per-ray counts, and the step's ONE
+ *   ugrid_voxgo_step_sample    ugrid_train_sample_dvgo / _dcvgo / _mpi / ugrid_train_sample, the prefix sums of the two per-ray counts, and the step's ONE
  *                              host read: M1 (stage-1 samples the backward walks) and M2 (samples that reach the rgbnet) are
  *                              written into the struct.  Synchronises `stream` (not with sync_free, below).
  *   (the caller sizes the per-sample buffers: ws = ugrid_voxgo_step_ws_floats floats; the visible outputs below)
@@ -568,8 +568,13 @@ int ugrid_train_sample_compact_vox(int64_t n_rays, int32_t slots_per_ray, float 
  * Device pointers unless marked HOST.  mode 0: DirectVoxGO (near / far / stepdist / slots used), 1: DirectContractedVoxGO
  * (t_table[slots] / scene_center / scene_radius / bg_len / norm_l2 / dist_thres used), 2: FourierGridModel
  * (FourierGrid_model.py:509-672: ugrid_train_sample over the Fourier density grid, no mask cache; t_table / scene_center /
- * scene_radius / bg_len / norm_l2 and the two grids' levels used).  bg: [n_rays,3] or NULL.  coef9: see
- * ugrid_render_loss.  inner2 may be NULL.  ugrid_voxgo_step_sizeof = sizeof(ugrid_voxgo_step), for bindings to check their mirror. */
+ * scene_radius / bg_len / norm_l2 and the two grids' levels used), 3: DirectMPIGO (dmpigo.py:251-340, the forward-facing model:
+ * ugrid_train_sample_mpi with plane_shift[mpi_depth] -- the act_shift.grid parameter itself, which receives no gradient --, slots =
+ * n_steps >= 2 samples per ray, the scalar act_shift ignored (the march stores density + shift: the compaction and the sampling's
+ * backward run with shift 0), and t_table[slots] = the samples' normalised distances s_j = (j + 0.5) / n_steps: the compaction
+ * writes t2 = t_table[step], and t2 is handed to ugrid_render_loss(_backward) as BOTH s and t, as the op-by-op step does -- modes
+ * 0-2 pass s = NULL).  Mode 3 needs P == 1, freq_num == 0, kP == 1, mask / t_table / plane_shift non-NULL, 1 <= mpi_depth <= 256.
+ * bg: [n_rays,3] or NULL.  coef9: see ugrid_render_loss.  inner2 may be NULL (mode 3: not written).  ugrid_voxgo_step_sizeof = sizeof(ugrid_voxgo_step), for bindings to check their mirror. */
 typedef struct ugrid_voxgo_step {
   int32_t mode;
   int32_t k0_channels_last; /* k0_grid / grad_k0_grid stored [P][X][Y][Z][C] */
@@ -578,7 +583,7 @@ typedef struct ugrid_voxgo_step {
   int32_t X, Y, Z;          /* density grid [P,1,X,Y,Z] (canonical) */
   int32_t kX, kY, kZ, C;    /* k0 grid [kP,C,kX,kY,kZ] */
   int32_t pe, width;        /* viewbase_pe; rgbnet width (<= 128; C + 3 + 6 pe <= 128) */
-  int32_t slots;            /* scratch slots per ray (mode 0: >= the longest ray's step count; mode 1: the table length) */
+  int32_t slots;            /* scratch slots per ray (mode 0: >= the longest ray's step count; modes 1, 2: the table length; mode 3: n_steps) */
   int32_t norm_l2;
   int32_t mask_dims[3];     /* HOST */
   float mask_scale[3], mask_shift[3], scene_center[3], scene_radius[3]; /* HOST */
@@ -616,6 +621,9 @@ typedef struct ugrid_voxgo_step {
   float *g_w0, *g_b0, *g_w1, *g_b1, *g_w2, *g_b2;
   float *grad_density_grid, *grad_k0_grid;
   uint32_t *touch;          /* touched-line bitmap of grad_k0_grid, or NULL */
+  /* mode 3 (appended: no earlier field moves) */
+  const float *plane_shift; /* [mpi_depth]: the per-plane density shift (DirectMPIGO's act_shift.grid), read by the march */
+  int32_t mpi_depth;
 } ugrid_voxgo_step;
 int64_t ugrid_voxgo_step_sizeof(void);
 int64_t ugrid_voxgo_step_ws_floats(const ugrid_voxgo_step *s);

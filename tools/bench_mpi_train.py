@@ -8,6 +8,11 @@ step clocked on the host between device synchronisations; the medians are report
 
     python tools/bench_mpi_train.py [--steps 20] [--warmup 4] [--phase dense|masked|both] [--out profiles/mpi/bench_mpi_train.txt]
 
+`--arms native` measures what the native step (native_step.VoxGOStep mode 'mpi') is worth instead, three arms alternating in the same
+way: (a) the fused op-by-op step (native_step = False: four autograd nodes, the yardstick), (b) the native step with its one host
+read, (c) the native step sync-free (native_sync_free = True, train_iteration(return_tensors=True): no host read in the step; the
+clock still stops at a device synchronisation).  Default --out then: profiles/mpi/bench_mpi_train_native.txt.
+
 One JSON line per TV phase.  Trained-like grids (tools/bench_mpi.py's scene: a smooth front surface + noise, free space masked),
 4096 random rays of a 1008 x 756 NDC view per step."""
 import argparse
@@ -55,6 +60,58 @@ def view_rays(dev):
     return [x.reshape(-1, 3).contiguous() for x in get_rays_of_a_view(H, W, K, c2w, ndc=True)]
 
 
+def _arm(native_step, sync_free=False, **it_kw):
+    def set_(m):
+        m.fused_forward, m.native_step, m.native_sync_free = True, native_step, sync_free
+    return set_, it_kw
+
+
+NATIVE_ARMS = {"a_fused_op_by_op": _arm(False), "b_native": _arm(True), "c_native_sync_free": _arm(True, True, return_tensors=True)}
+
+
+def run_native(args, first_step, dev):
+    """the three arms of --arms native, alternating step by step on one model and optimizer"""
+    from unboundednerfpytorch_amd import train_step as ts
+    from unboundednerfpytorch_amd.train_utils import create_optimizer_or_freeze_model
+    m = make_model(dev)
+    opt = create_optimizer_or_freeze_model(m, CFG, global_step=0)
+    o_all, d_all, v_all = view_rays(dev)
+    rk = dict(near=0, far=1, stepsize=STEPSIZE, bg=1, rand_bkgd=True)
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    names = list(NATIVE_ARMS)
+    ms = {n: [] for n in names}
+    for it in range(len(names) * (args.warmup + args.steps)):
+        name = names[it % len(names)]
+        set_, it_kw = NATIVE_ARMS[name]
+        sel = torch.randint(o_all.shape[0], [CFG['N_rand']], device=dev, generator=g)
+        o, d, v = o_all[sel], d_all[sel], v_all[sel]
+        rgb = torch.rand(CFG['N_rand'], 3, device=dev, generator=g)
+        set_(m)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        loss, psnr = ts.train_iteration(m, opt, o, d, v, rgb, CFG, first_step + it, rk, **it_kw)
+        torch.cuda.synchronize()
+        if it >= len(names) * args.warmup:
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    with torch.no_grad():
+        out = m(o, d, v, global_step=1, **rk)
+    res = {"workload": "DirectMPIGO train step (llff_default fine stage), native-step arms: world %s, mpi_depth %d, C=9, width 64, %d rays of a "
+                       "1008x756 NDC view, stepsize %.1f, TV %s" % (m.world_size.tolist(), D, CFG['N_rand'], STEPSIZE,
+                                                                    "dense" if first_step < CFG['tv_dense_before'] else "masked"),
+           "samples_per_ray": m.n_samples(STEPSIZE), "survivors_M": int(out["weights"].numel()), "steps_each": args.steps}
+    for n in names:
+        res[n + "_ms_per_step"] = float(np.median(ms[n]))
+        res[n + "_ms_min_max"] = [min(ms[n]), max(ms[n])]
+    a = res["a_fused_op_by_op_ms_per_step"]
+    res["b_over_a"], res["c_over_a"] = res["b_native_ms_per_step"] / a, res["c_native_sync_free_ms_per_step"] / a
+    # the gate: (b) not slower than (a) by more than (a)'s own min-max range in this run
+    res["a_range_ms"] = res["a_fused_op_by_op_ms_min_max"][1] - res["a_fused_op_by_op_ms_min_max"][0]
+    res["b_within_a_range"] = bool(res["b_native_ms_per_step"] <= a + res["a_range_ms"])
+    res["loss"], res["device"] = float(loss), torch.cuda.get_device_name(0)
+    return res
+
+
 def run(args, first_step, dev):
     from unboundednerfpytorch_amd import train_step as ts
     from unboundednerfpytorch_amd.train_utils import create_optimizer_or_freeze_model
@@ -71,7 +128,7 @@ def run(args, first_step, dev):
         sel = torch.randint(o_all.shape[0], [CFG['N_rand']], device=dev, generator=g)
         o, d, v = o_all[sel], d_all[sel], v_all[sel]
         rgb = torch.rand(CFG['N_rand'], 3, device=dev, generator=g)
-        m.fused_forward = fused
+        m.fused_forward, m.native_step = fused, False      # (the fused step of this comparison is the op-by-op one: four autograd nodes)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss, psnr = ts.train_iteration(m, opt, o, d, v, rgb, CFG, first_step + it, rk)
@@ -96,13 +153,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="timed steps of EACH variant (alternating)")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--phase", default="both")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mpi", "bench_mpi_train.txt"))
+    ap.add_argument("--arms", default="fused", choices=["fused", "native"], help="fused vs op-by-op chain | the three native-step arms")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mpi", "bench_mpi_train_native.txt" if args.arms == "native" else "bench_mpi_train.txt")
     assert args.steps >= 20, "median of at least 20 steps"
     dev = torch.device("cuda", 0)
     lines = []
     for first in {"dense": [1], "masked": [10001]}.get(args.phase, [1, 10001]):
-        lines.append(json.dumps(run(args, first, dev)))
+        lines.append(json.dumps((run_native if args.arms == "native" else run)(args, first, dev)))
         print(lines[-1], flush=True)
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -2,8 +2,8 @@
 """How far apart are two runs of the SAME training step?  (VERDICT r5 item 2 / ADVICE r5 medium.)
 
 The grid lookups' backward scatters with hardware fp32 atomics: the same terms, summed in an order that differs run to run.  The
-two native-step tests (tests/test_gpu_train_scale.py::test_native_step_equals_the_op_by_op_step, tests/test_gpu_voxgo_train.py::
-test_native_step_equals_the_op_by_op_step) compare native_step.VoxGOStep with the op-by-op step; their bounds must come from the
+native-step tests (tests/test_gpu_train_scale.py::test_native_step_equals_the_op_by_op_step, tests/test_gpu_voxgo_train.py::
+test_native_step_equals_the_op_by_op_step, tests/test_gpu_mpi_native.py -- `--cases mpi --out profiles/mpi/native_step_spread.json`) compare native_step.VoxGOStep with the op-by-op step; their bounds must come from the
 spread two op-by-op runs show against EACH OTHER, not from a guess.  For every configuration of those tests this tool repeats, `--reps`
 times with fresh models of the same seed:
 
@@ -156,6 +156,43 @@ def voxgo_case(kind, dev):
     return res
 
 
+def mpi_case(dev):
+    """tests/test_gpu_mpi_native.py: test_native_step_equals_the_op_by_op_step and test_short_training_trajectories_stay_together"""
+    import test_gpu_mpi_native as T
+    from unboundednerfpytorch_amd import train_step as ts
+    from unboundednerfpytorch_amd.train_utils import create_optimizer_or_freeze_model
+    torch.manual_seed(0)
+    m0, (o, d, v), rk, fl = T.setup(dev, rand_bkgd=True)
+    cfg = dict(T.LLFF, lrate_density=1e-1, lrate_k0=1e-1, lrate_rgbnet=1e-3, lrate_decay=20, pg_scale=[], tv_every=1, tv_after=0, tv_before=7,
+               tv_dense_before=4, weight_tv_density=1e-5, weight_tv_k0=1e-6, skip_zero_grad_fields=['density', 'k0'])
+    models = []
+    for native in (True, False, False):
+        m = copy.deepcopy(m0)
+        m.native_step = native
+        models.append(m)
+    outs = []
+    for m in models:
+        torch.manual_seed(5)
+        out = m(o, d, v, global_step=1, is_train=True, fused_loss=fl, **rk)
+        out["loss"].backward()
+        outs.append((out, {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}))
+        m.zero_grad(set_to_none=True)
+    res = {"native_is_native": type(outs[0][0]["loss"].grad_fn).__name__.startswith("VoxGOStep"),
+           "fwd_equal": _fwd_equal(outs[0][0], outs[1][0]), "samples": int(outs[1][0]["weights"].numel())}
+    res["grid_grad_native_vs_op"], res["fixed_grads_equal_native_vs_op"] = _grad_metrics(outs[0][1], outs[1][1])
+    res["grid_grad_op_vs_op"], res["fixed_grads_equal_op_vs_op"] = _grad_metrics(outs[2][1], outs[1][1])
+    traj = []
+    for m in models:
+        torch.manual_seed(11)
+        opt = create_optimizer_or_freeze_model(m, cfg, global_step=0)
+        losses = [ts.train_iteration(m, opt, o, d, v, fl['target'], cfg, step, rk) for step in range(1, 9)]
+        torch.cuda.synchronize()
+        traj.append((losses, {k: p.detach().clone() for k, p in m.named_parameters()}))
+    res["traj_native_vs_op"] = _traj_metrics(traj[0], traj[1])
+    res["traj_op_vs_op"] = _traj_metrics(traj[2], traj[1])
+    return res
+
+
 def summarise(reps):
     """maxima over the repetitions + the bounds the tests assert"""
     def mx(path):
@@ -197,6 +234,8 @@ def main():
         for i in range(a.reps):
             if name.startswith("fourier"):
                 reps.append(fourier_case(name.endswith("True"), dev))
+            elif name == "mpi":
+                reps.append(mpi_case(dev))
             else:
                 reps.append(voxgo_case(name, dev))
             torch.cuda.empty_cache()

@@ -98,6 +98,7 @@ class VoxgoStep(_c.Structure):
         ("grad_loss", _P), ("ws_bwd", _P),
         ("g_w0", _P), ("g_b0", _P), ("g_w1", _P), ("g_b1", _P), ("g_w2", _P), ("g_b2", _P),
         ("grad_density_grid", _P), ("grad_k0_grid", _P), ("touch", _P),
+        ("plane_shift", _P), ("mpi_depth", _c.c_int32),
     ]
 
 

@@ -1,4 +1,5 @@
-// One training step of the two dense-grid models issued natively (include/ugrid_hip.h: ugrid_voxgo_step).
+// One training step of the dense-grid models (DirectVoxGO, DirectContractedVoxGO, DirectMPIGO) and of FourierGridModel issued
+// natively (include/ugrid_hip.h: ugrid_voxgo_step, modes 0-3).
 //
 // The op-by-op step (voxgo_model.py + train_step.py) is host-bound: ~30 launches through Python + ctypes + four autograd nodes
 // take ~0.9 ms to issue for 0.8 ms of GPU time.  Nothing here is a new algorithm: the three entry points call
@@ -100,17 +101,24 @@ extern "C" int64_t ugrid_voxgo_step_ws_floats(const ugrid_voxgo_step *s) { retur
 extern "C" int64_t ugrid_voxgo_step_bwd_ws_floats(const ugrid_voxgo_step *s) { return ug_step_layout_bwd(s).total; }
 
 static int ug_step_check(const ugrid_voxgo_step *s) {
-  if (!s || s->mode < 0 || s->mode > 2 || s->n_rays <= 0 || s->slots <= 0 || s->C < 1 || s->pe < 0 || s->P < 1 || s->kP < 1 ||
+  if (!s || s->mode < 0 || s->mode > 3 || s->n_rays <= 0 || s->slots <= 0 || s->C < 1 || s->pe < 0 || s->P < 1 || s->kP < 1 ||
       s->freq_num < 0 || s->k0_freq_num < 0)
     return (int)hipErrorInvalidValue;
   if (s->mode != 2 && (s->P != 1 || s->freq_num != 0)) return (int)hipErrorInvalidValue;       // the dense-grid models' density grid
   if (s->P != 1 + 2 * s->freq_num && !(s->P == 1 && s->freq_num == 0)) return (int)hipErrorInvalidValue;
   if (s->kP != 1 + 2 * s->k0_freq_num && !(s->kP == 1 && s->k0_freq_num == 0)) return (int)hipErrorInvalidValue;
+  // DirectMPIGO: one level each, the per-plane shift table the march reads, a mask cache, the s table, ugrid_train_sample_mpi's limits
+  if (s->mode == 3 && (s->kP != 1 || !s->plane_shift || !s->mask || !s->t_table || s->mpi_depth < 1 || s->mpi_depth > 256 || s->slots < 2))
+    return (int)hipErrorInvalidValue;
   if (s->width < 1 || s->width > 128 || s->C + 3 + 6 * s->pe > 128) return (int)hipErrorNotSupported;
   if (s->sync_free && (s->M1 < s->n_rays * (int64_t)s->slots || s->M2 < 1 || s->M2 > s->M1 || s->hint1 < 0 || s->hint2 < 0))
     return (int)hipErrorInvalidValue;                    // capacities: stage 1 cannot overflow, stage 2 is clamped by the compaction
   return 0;
 }
+// DirectMPIGO (mode 3): the march stored density + per-plane shift, so Raw2Alpha's own shift is 0 in the compaction and the sampling's
+// backward; and the loss takes the samples' s explicitly -- t2, the s table's entries -- where the other modes derive it from t
+static inline float ug_step_shift(const ugrid_voxgo_step *s) { return s->mode == 3 ? 0.f : s->act_shift; }
+static inline const float *ug_step_s(const ugrid_voxgo_step *s) { return s->mode == 3 ? s->t2 : nullptr; }
 // the count of the step's stage-1 / stage-2 arrays as the kernels see it: on the device (sync_free) or the host's number
 #define UG_STEP_ROWS1(s) ug_devn_scope rows_scope_((s)->sync_free ? (s)->totals : nullptr, (s)->hint1, 0)
 #define UG_STEP_ROWS2(s) ug_devn_scope rows_scope_((s)->sync_free ? (s)->totals + 1 : nullptr, (s)->hint2, (s)->sync_free ? (s)->M2 : 0)
@@ -120,7 +128,11 @@ extern "C" int ugrid_voxgo_step_sample(ugrid_voxgo_step *s, ugrid_stream_t st) {
   if (rc) return rc;
   const int64_t R = s->n_rays;
   int32_t *c1 = s->counts, *c2 = s->counts + R;
-  if (s->mode == 2)
+  if (s->mode == 3)
+    rc = ugrid_train_sample_mpi(s->density_grid, s->X, s->Y, s->Z, s->rays_o, s->rays_d, R, s->slots, s->xyz_min, s->xyz_max, s->plane_shift,
+                                s->mpi_depth, s->mask, s->mask_dims, s->mask_scale, s->mask_shift, s->interval, s->thres, s->sc_pts,
+                                s->sc_density, s->sc_step, s->sc_w, s->sc_T, c1, c2, s->alphainv_last, st);
+  else if (s->mode == 2)
     rc = ugrid_train_sample(s->density_grid, s->P, s->X, s->Y, s->Z, s->freq_num, s->rays_o, s->rays_d, R, s->t_table, s->slots,
                             s->scene_center, s->scene_radius, s->xyz_min, s->xyz_max, s->bg_len, s->norm_l2, s->act_shift, s->interval,
                             s->thres, s->sc_pts, s->sc_density, s->sc_step, s->sc_w, s->sc_T, c1, c2, s->alphainv_last, st);
@@ -154,14 +166,16 @@ extern "C" int ugrid_voxgo_step_forward(const ugrid_voxgo_step *s, ugrid_stream_
   const int64_t R = s->n_rays, M2 = s->M2;
   const int K = s->C + 3 + 6 * s->pe;
   UG_STEP_ROWS2(s);
+  const float shift = ug_step_shift(s);
   if (s->M1 > 0 && s->mode == 2) {
     rc = ugrid_train_sample_compact(R, s->slots, s->act_shift, s->interval, s->thres, s->sc_pts, s->sc_density, s->sc_step, s->sc_w, s->sc_T,
                                     s->counts, s->offsets, s->counts + R, s->offsets + R, s->t_table, w.pts1, w.dens1, w.w1, w.T1, w.pos2,
                                     w.pts2, s->density2, s->alpha2, s->weights2, s->ray_id2, s->step_id2, s->t2, st);
     if (rc) return rc;
   } else if (s->M1 > 0) {
-    rc = ugrid_train_sample_compact_vox(R, s->slots, s->act_shift, s->interval, s->thres, s->sc_pts, s->sc_density, s->sc_step, s->sc_w,
-                                        s->sc_T, s->counts, s->offsets, s->counts + R, s->offsets + R, s->mode == 1 ? s->t_table : nullptr,
+    // the table entry of a sample's step goes to t2: the contracted model's distances, DirectMPIGO's s; DirectVoxGO has none
+    rc = ugrid_train_sample_compact_vox(R, s->slots, shift, s->interval, s->thres, s->sc_pts, s->sc_density, s->sc_step, s->sc_w,
+                                        s->sc_T, s->counts, s->offsets, s->counts + R, s->offsets + R, s->mode != 0 ? s->t_table : nullptr,
                                         w.pts1, w.dens1, w.w1, w.T1, w.pos2, w.pts2, s->density2, s->alpha2, s->weights2, s->ray_id2,
                                         s->step_id2, s->t2, s->mode == 1 ? s->inner2 : nullptr, st);
     if (rc) return rc;
@@ -173,7 +187,7 @@ extern "C" int ugrid_voxgo_step_forward(const ugrid_voxgo_step *s, ugrid_stream_
   if (rc) return rc;
   rc = ugrid_rgbnet_train_forward(w.feat, M2, K, s->w0, s->b0, s->w1, s->b1, s->w2, s->b2, s->width, w.h1, w.h2, s->logits, st);
   if (rc) return rc;
-  return ugrid_render_loss(s->logits, s->weights2, nullptr, s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9, s->seg,
+  return ugrid_render_loss(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9, s->seg,
                            s->rgb_marched, s->ray_tot, s->partial, s->out2, st);
 }
 
@@ -187,7 +201,7 @@ extern "C" int ugrid_voxgo_step_backward_k0(const ugrid_voxgo_step *s, ugrid_str
   const int64_t R = s->n_rays, M2 = s->M2;
   const int K = s->C + 3 + 6 * s->pe;
   UG_STEP_ROWS2(s);
-  rc = ugrid_render_loss_backward(s->logits, s->weights2, nullptr, s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9,
+  rc = ugrid_render_loss_backward(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9,
                                   s->seg, s->rgb_marched, s->ray_tot, s->grad_loss, b.g_logits, b.g_w, b.g_ainv, b.g_dens, st);
   if (rc) return rc;
   rc = ugrid_rgbnet_train_backward(b.g_logits, w.feat, w.h1, w.h2, M2, K, s->C, s->w0, s->w1, s->w2, s->width, b.g_k0, s->g_w0, s->g_b0,
@@ -209,7 +223,7 @@ extern "C" int ugrid_voxgo_step_backward_density(const ugrid_voxgo_step *s, ugri
   const ug_step_ws w = ug_step_layout(s);
   const ug_step_ws_bwd b = ug_step_layout_bwd(s);
   UG_STEP_ROWS1(s);
-  rc = ugrid_train_sample_backward(s->n_rays, s->act_shift, s->interval, w.dens1, w.w1, w.T1, w.pos2, s->counts, s->offsets, s->alphainv_last,
+  rc = ugrid_train_sample_backward(s->n_rays, ug_step_shift(s), s->interval, w.dens1, w.w1, w.T1, w.pos2, s->counts, s->offsets, s->alphainv_last,
                                    b.g_w, b.g_ainv, b.g_dens, b.g1, st);
   if (rc) return rc;
   return ugrid_grid_query_backward(b.g1, s->P, 1, s->X, s->Y, s->Z, w.pts1, s->xyz_min, s->xyz_max, s->freq_num, s->M1, s->grad_density_grid,

@@ -13,7 +13,14 @@ frequencies runs on the fp32-MFMA kernels (ops.FusedRgbnet), and train_step.trai
 s = (step_id + 0.5) / N_samples.  `fused_forward = False` selects the op-by-op chain over the drop-in ops (the A/B twin of the
 tests).  Inference should use mpi_render.DirectMPIGORenderer.  There is no CPU path: the ops raise without the HIP library.
 
-Not covered: native_step.VoxGOStep (the step as one autograd node issued from C) and data-parallel training."""
+With train_iteration's fused loss the fine stage (the default 3-layer rgbnet, every parameter trainable) takes the NATIVE step like
+the other dense-grid models: native_step.VoxGOStep mode 'mpi' -- the same kernels on the same sizes in the same order as ONE autograd
+node issued from C (ugrid_voxgo_step mode 3), the k0 update started between the two backward halves, and with `native_sync_free`
+no host read at all, so the step can be captured in a hipGraph.  The per-plane shift is handed over as a device pointer and gets no
+gradient; the samples' s come from the table sample_table() holds.  `native_step = False` keeps the four-node op-by-op step (the
+tests' twin).  The coarse stage (no rgbnet) and non-default rgbnets stay on the op-by-op ops.
+
+Not covered: data-parallel training."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -26,7 +33,7 @@ from .voxgo_model import _VoxGOBase
 
 class DirectMPIGO(_VoxGOBase):
     """The forward-facing model (dmpigo.py:18-340)."""
-    native_step = False         # (native_step.VoxGOStep has no MPI mode)
+    native_step = True          # native_step.VoxGOStep mode 'mpi' (fine stage, train_iteration's fused loss); False: the op-by-op step
     fused_loss = True           # train_step.train_iteration: compositing + loss as ops.RenderLoss
 
     def __init__(self, xyz_min, xyz_max, num_voxels=0, mpi_depth=0, mask_cache_path=None, mask_cache_thres=1e-3,
@@ -197,6 +204,22 @@ class DirectMPIGO(_VoxGOBase):
             cfg = {'mode': 'mpi', 'interval': float(interval), 'thres': float(self.fast_color_thres), 'mask_scale': hc['mask_scale'],
                    'mask_shift': hc['mask_shift'], 'n_steps': N_samples, 'mpi_depth': int(self.mpi_depth),
                    'act_shift': self.act_shift.get_dense_grid().detach().reshape(-1)}
+            fl = render_kwargs.get('fused_loss')
+            native = self._native_params() if fl is not None else None
+            if native is not None:
+                # the whole step as one autograd node (native_step.VoxGOStep 'mpi'): the s table stands for (step_id + 0.5) / N_samples,
+                # the nearclip term cannot apply (no raw density, no t in the reference's dict: its coefficient is zeroed, as below)
+                coef = list(fl['coef'])
+                coef[4] = coef[5] = 0.0
+                bg = 'rand' if (render_kwargs.get('rand_bkgd', False) and global_step is not None) else render_kwargs['bg']
+                out = self._native_forward(native, 'mpi', cfg, self.sample_table(stepsize, dev), rays_o.contiguous(), rays_d.contiguous(),
+                                           viewdirs, {'target': fl['target'], 'coef': coef}, self._bg_rows(N, dev, bg, cached=True),
+                                           self.mask_cache.mask)
+                for k in ('raw_density', 'step_id'):       # (not in DirectMPIGO's return dict, dmpigo.py:320-340)
+                    out.pop(k)
+                out['s'] = out.pop('t')
+                out['n_max'] = N_samples
+                return out
             pts, density, alpha, weights, alphainv_last, ray_id, step_id, _, _ = _grid.TrainSampleVox.apply(
                 self.density.grid, rays_o.contiguous(), rays_d.contiguous(), None, self.xyz_min, self.xyz_max, self.mask_cache.mask, cfg)
         else:

@@ -1,7 +1,8 @@
-"""The training step of the dense-grid models and of FourierGridModel issued natively: ONE autograd node whose forward is two C calls
+"""The training step of the dense-grid models (DirectVoxGO, DirectContractedVoxGO, DirectMPIGO) and of FourierGridModel issued
+natively: ONE autograd node whose forward is two C calls
 (include/ugrid_hip.h: ugrid_voxgo_step_sample / _forward) and whose backward is one (ugrid_voxgo_step_backward), in place of the
 op-by-op step's four nodes and ~30 launches issued from Python (train_model.py and its subclasses in voxgo_model.py /
-fourier_model.py: TrainSampleVox / TrainSample, the k0 GridQuery, FusedRgbnet, RenderLoss).  The models reach it through
+fourier_model.py / mpi_model.py: TrainSampleVox / TrainSample, the k0 GridQuery, FusedRgbnet, RenderLoss).  The models reach it through
 TrainModel._native_params / _native_forward; its march scratch is grid.scratch, shared with those sample ops.
 The C side runs the same kernels on the same sizes in the same order, so loss, outputs and every gradient are the
 op-by-op step's (tests/test_gpu_voxgo_train.py, tests/test_gpu_train_step.py: bit for bit where sums have a fixed order); what changes is the host time between launches.
@@ -68,9 +69,11 @@ def _coef9(coef):
 
 class VoxGOStep(torch.autograd.Function):
     """forward(density_grid [P,1,X,Y,Z], k0_grid [P,C,X,Y,Z], w0, b0, w1, b1, w2, b2, pack) -> loss, mse
-    pack (dict, not differentiated): mode 'dvgo' | 'dcvgo' | 'fourier', cfg (the dict TrainSampleVox takes; 'fourier': act_shift,
+    pack (dict, not differentiated): mode 'dvgo' | 'dcvgo' | 'fourier' | 'mpi', cfg (the dict TrainSampleVox takes -- 'mpi': n_steps,
+    mpi_depth, act_shift = the DEVICE tensor of the per-plane shift, interval, thres, mask_scale, mask_shift --; 'fourier': act_shift,
     interval, thres, scene_center, scene_radius, bg_len, norm_l2, freq_num, k0_freq_num), rays_o / rays_d / viewdirs [R,3],
-    viewfreq [pe], t (dcvgo, fourier: the sample table [S]), xyz_min / xyz_max, k0_xyz_min / k0_xyz_max, mask (bool [mi,mj,mk];
+    viewfreq [pe], t (dcvgo, fourier: the sample table [S]; mpi: the s table (j + 0.5) / n_steps, [n_steps] -- the `t` output is
+    then the samples' s, and the loss takes it as both s and t), xyz_min / xyz_max, k0_xyz_min / k0_xyz_max, mask (bool [mi,mj,mk];
     none for 'fourier'), target [R,3], bg [R,3] or None, coef (ops.loss_coefficients).
     pack['sync_free'] (optional: True or {'capacity': rows of the stage-2 arrays (default rays x slots: cannot overflow), 'hints': (M1, M2)
     expected counts}): the step makes no host read and synchronises nothing -- forward and backward only enqueue work, the whole step can
@@ -105,6 +108,18 @@ class VoxGOStep(torch.autograd.Function):
         if t_tab is not None:
             t_tab = t_tab.contiguous()
             f32.append(("t", t_tab))
+        shift_tab = None
+        if mode == 'mpi':
+            # the checks grid.TrainSampleVox makes for 'mpi': the per-plane shift is read by the march from device memory
+            shift_tab = cfg['act_shift']
+            n_steps, depth = int(cfg['n_steps']), int(cfg['mpi_depth'])
+            _lib.require_cuda(("act_shift", shift_tab))
+            _lib.require_f32(("act_shift", shift_tab))
+            if n_steps < 2 or not 1 <= depth <= 256 or shift_tab.numel() != depth or not shift_tab.is_contiguous() \
+                    or shift_tab.device != density_grid.device:
+                raise RuntimeError("mpi: n_steps >= 2, 1 <= mpi_depth <= 256 and a contiguous act_shift of mpi_depth values on the grid's device")
+            if t_tab is None or t_tab.numel() != n_steps or mask is None:
+                raise RuntimeError("VoxGOStep: 'mpi' needs the mask cache and t = the s table (j + 0.5) / n_steps of n_steps = %d entries" % n_steps)
         if mask is not None and (mask.dtype != torch.bool or mask.dim() != 3):
             raise RuntimeError("VoxGOStep: mask must be a bool tensor [mi,mj,mk] (got %s, %d-D)" % (mask.dtype, mask.dim()))
         _lib.require_cuda(*f32, *([("mask", mask)] if mask is not None else []))
@@ -123,7 +138,7 @@ class VoxGOStep(torch.autograd.Function):
         dev = density_grid.device
         R = rays_o.shape[0]
         t = t_tab
-        S = int(cfg['slots']) if mode == 'dvgo' else t.numel()
+        S = int(cfg['slots']) if mode == 'dvgo' else int(cfg['n_steps']) if mode == 'mpi' else t.numel()
         C, W, pe = k0_grid.shape[1], ws_[0].shape[0], viewfreq.numel()
         if tuple(ws_[0].shape) != (W, C + 3 + 6 * pe) or tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W):
             raise RuntimeError("VoxGOStep: rgbnet weights must be [W, C+3+6pe], [W,W], [3,W]")
@@ -137,7 +152,7 @@ class VoxGOStep(torch.autograd.Function):
         rgb_marched = torch.empty(R, 3, device=dev)
         out2 = torch.empty(2, device=dev)
         s = _lib.VoxgoStep()
-        s.mode = {'dvgo': 0, 'dcvgo': 1, 'fourier': 2}[mode]
+        s.mode = {'dvgo': 0, 'dcvgo': 1, 'fourier': 2, 'mpi': 3}[mode]
         s.k0_channels_last = int(k0_cl)
         s.P, s.kP = density_grid.shape[0], k0_grid.shape[0]
         s.freq_num, s.k0_freq_num = (max(int(cfg['freq_num']), 0), max(int(cfg['k0_freq_num']), 0)) if mode == 'fourier' else (0, 0)
@@ -149,8 +164,12 @@ class VoxGOStep(torch.autograd.Function):
             s.mask_scale[:] = cfg['mask_scale']
             s.mask_shift[:] = cfg['mask_shift']
             s.mask = mask.data_ptr()
-        s.act_shift, s.interval, s.thres = float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres'])
-        if mode == 'dvgo':
+        # ('mpi': the shift is a table, part of the density the march stores; Raw2Alpha's own shift is 0)
+        s.act_shift, s.interval, s.thres = (0.0 if mode == 'mpi' else float(cfg['act_shift'])), float(cfg['interval']), float(cfg['thres'])
+        if mode == 'mpi':
+            s.plane_shift, s.mpi_depth = shift_tab.data_ptr(), int(cfg['mpi_depth'])
+            s.t_table = t.data_ptr()
+        elif mode == 'dvgo':
             s.near_clip, s.far_clip, s.stepdist = float(cfg['near']), float(cfg['far']), float(cfg['stepdist'])
         else:
             s.scene_center[:] = cfg['scene_center']
@@ -206,7 +225,7 @@ class VoxGOStep(torch.autograd.Function):
             _lib.check(_L.ugrid_voxgo_step_forward(ps, st), "voxgo_step_forward")
         ctx.step = s
         # everything the struct points to stays alive until the backward has been issued
-        ctx.keep = (density_grid, k0_grid, ws_, rays_o, rays_d, viewdirs, target, bg, viewfreq, t, mask, box, sc, counts, i64, perray, ainv, rgb_marched, out2, ws, f4, ids, logits, inner)
+        ctx.keep = (density_grid, k0_grid, ws_, rays_o, rays_d, viewdirs, target, bg, viewfreq, t, shift_tab, mask, box, sc, counts, i64, perray, ainv, rgb_marched, out2, ws, f4, ids, logits, inner)
         ctx.shapes = (tuple(density_grid.shape), tuple(density_grid.stride()), tuple(k0_grid.shape), tuple(k0_grid.stride()), k0_cl)
         ctx.keys = (_gradpool.key_of(density_grid), _gradpool.key_of(k0_grid))
         ctx.wshapes = [tuple(x.shape) for x in ws_]
