@@ -82,6 +82,28 @@ int ugrid_maskcache_lookup(const uint8_t *world, const float *xyz, const float *
                            const float *xyz2ijk_shift, int64_t sz_i, int64_t sz_j, int64_t sz_k,
                            int64_t n_pts, uint8_t *out, ugrid_stream_t stream);
 
+/* NEW (no reference counterpart): DirectVoxGO.hit_coarse_geo (dvgo.py:291-304: the ray filter of the 'in_maskcache' sampler) as ONE
+ * kernel, one lane per ray, in place of sample_pts_on_rays + a boolean index + maskcache_lookup + a scatter.  A ray walks the samples
+ * ugrid_sample_pts_on_rays_count / _fill would give it (same t_min, step count, point and out-of-box test, through the same device
+ * functions), looks the in-box ones up as ugrid_maskcache_lookup does and stops at the first occupied cell: hit [n_rays] (uint8
+ * bool, fully written) equals the composed result bit for bit; no sample is stored and nothing is read back.
+ * mask [mi,mj,mk] uint8 bool; xyz2ijk_scale / _shift: DEVICE [3]. */
+int ugrid_hit_coarse_geo(const float *rays_o, const float *rays_d, int64_t n_rays, const float *xyz_min,
+                         const float *xyz_max, float near, float far, float stepdist, const uint8_t *mask,
+                         int64_t mi, int64_t mj, int64_t mk, const float *xyz2ijk_scale,
+                         const float *xyz2ijk_shift, uint8_t *hit, ugrid_stream_t stream);
+
+/* NEW (no reference counterpart): one image of voxel_count_views (dvgo.py:250-276) as two launches.
+ *   _accumulate: one lane per ray; for j < n_samples the point o + d * (t_min + (stepdist * j) / |d|), t_min as
+ *                ugrid_infer_t_minmax forms it, adds its trilinear corner weights (zero padding: the taps of
+ *                ugrid_grid_query_backward with gradient 1) into acc [X,Y,Z] with fp32 atomics -- what the backward of a lookup
+ *                on the materialised points adds, in another order.  A ray ends early only where no later sample can reach the grid.
+ *   _commit:     count[v] += acc[v] > 1 ? 1 : 0;  acc[v] = 0  (n = X*Y*Z; acc must be zero before the first image). */
+int ugrid_count_views_accumulate(const float *rays_o, const float *rays_d, int64_t n_rays, const float *xyz_min,
+                                 const float *xyz_max, float near, float far, float stepdist, int32_t n_samples,
+                                 int X, int Y, int Z, float *acc, ugrid_stream_t stream);
+int ugrid_count_views_commit(float *acc, float *count, int64_t n, ugrid_stream_t stream);
+
 /* replaces raw2alpha / raw2alpha_nonuni (render_utils.cpp:177-178 -> render_utils_kernel.cu:431-504).
  * interval_arr == NULL: uniform `interval`; else per-point intervals [n]. */
 int ugrid_raw2alpha(const float *density, float shift, float interval, const float *interval_arr,
@@ -609,7 +631,9 @@ typedef struct ugrid_voxgo_step {
   int64_t M1, M2;           /* written by ugrid_voxgo_step_sample; sync_free: set by the CALLER -- the rows the per-sample arrays hold */
   int64_t hint1, hint2;     /* sync_free: expected counts (e.g. the previous step's), size the launch grids only; 0 = M1 / M2 */
   int32_t sync_free;        /* 1: no host read anywhere in the step (below) */
-  int32_t reserved_;
+  int32_t colour;           /* 0: the rgbnet on all of k0; 1: no rgbnet (the coarse stage) -- C == 3, the k0 lookup writes `logits` itself
+                               and its scatter reads their gradient; w0 .. b2, g_w0 .. g_b2, viewdirs, viewfreq may be NULL, pe / width
+                               are not looked at and the workspaces hold nothing for the network.  Anything else: hipErrorInvalidValue */
   float *ws;
   float *density2, *alpha2, *weights2, *t2; /* [M2] */
   int64_t *ray_id2, *step_id2;              /* [M2] */

@@ -1,6 +1,7 @@
 // libugrid_hip.so -- march half of the fused render path + grid packing/query kernels.
 // Built with -fno-slp-vectorize (see ugrid_render.h header note and csrc/build.sh).
 #include "ugrid_render.h"
+#include "ugrid_rays.h"
 
 // ----------------------------------------------------------------------------------------------
 // brick packing: canonical [P,C,X,Y,Z] -> [P*(X-1)(Y-1)(Z-1)] cell records of [H halves][8][CH]
@@ -318,6 +319,58 @@ __global__ void k_grid_query_backward(const float *__restrict__ grad_out, int P,
   const int64_t total = (CL ? n * C : n) * P;
   for (int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tid < total; tid += (int64_t)gridDim.x * blockDim.x)
     ug_grid_query_backward_one<CL>(tid, grad_out, P, C, X, Y, Z, xyz, xyz_min, xyz_max, F, n, grad_grid, touch);
+}
+
+// ----------------------------------------------------------------------------------------------
+// voxel_count_views (dvgo.py:250-276): per image, the trilinear footprint of every sample of every ray is added into a zero grid
+// and a voxel counts as seen where it gathered more than 1.  The reference gets the footprint from the backward of a lookup on
+// materialised points ([10000, n_samples, 3] per chunk, an autograd backward per chunk); here one lane walks one ray and adds the
+// corner weights itself -- the point as that path forms it, o + d * (t_min + (stepdist * j) / |d|), the taps of the lookup's own
+// backward (ug_unorm + ug_tap_setup, gradient 1), the same hardware atomics: the same sums in another order.
+//   k_count_views_accumulate   one image's rays -> acc += footprint
+//   k_count_views_commit       count += acc > 1; acc = 0 (ready for the next image)
+// A ray stops where no later sample can reach the grid: zero padding gives a point up to ONE cell outside the box a weight on the
+// face vertices, a point is monotone in j on every axis, so two cells beyond a face it is leaving (or not moving towards) is final.
+// ----------------------------------------------------------------------------------------------
+__global__ void k_count_views_accumulate(const float *__restrict__ rays_o, const float *__restrict__ rays_d, int64_t n_rays,
+                                         const float *__restrict__ xyz_min, const float *__restrict__ xyz_max, float near, float far,
+                                         float stepdist, int32_t n_samples, int X, int Y, int Z, float *__restrict__ acc) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays) return;
+  const float lo[3] = {xyz_min[0], xyz_min[1], xyz_min[2]}, hi[3] = {xyz_max[0], xyz_max[1], xyz_max[2]};
+  const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]}, d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
+  const float t_min = ug_t_minmax(o, d, lo, hi, near, far).tmin;
+  const float rn = ug_norm3(d);
+  const int dims[3] = {X, Y, Z};
+  float below[3], above[3];                 // beyond these a point's eight corners are all outside the grid (two cells: one of slack)
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float two = 2.f * (hi[c] - lo[c]) / (float)(dims[c] - 1);
+    below[c] = lo[c] - two;
+    above[c] = hi[c] + two;
+  }
+  for (int32_t j = 0; j < n_samples; ++j) {
+    const float t = t_min + (stepdist * (float)j) / rn;
+    float p[3];
+    bool gone = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      p[c] = o[c] + d[c] * t;
+      gone |= (p[c] < below[c] && d[c] <= 0.f) || (p[c] > above[c] && d[c] >= 0.f);
+    }
+    if (gone) break;
+    const ug_taps tp = ug_tap_setup(X, Y, Z, ug_unorm(p[0], lo[0], hi[0]), ug_unorm(p[1], lo[1], hi[1]), ug_unorm(p[2], lo[2], hi[2]));
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (tp.off[c] >= 0 && tp.w[c] != 0.f) unsafeAtomicAdd(acc + tp.off[c], tp.w[c]);      // (adding an exact zero changes nothing)
+  }
+}
+
+__global__ void k_count_views_commit(float *__restrict__ acc, float *__restrict__ count, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    count[i] += acc[i] > 1.f ? 1.f : 0.f;
+    acc[i] = 0.f;
+  }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1071,6 +1124,26 @@ extern "C" int ugrid_grid_query_backward_cl_touch(const float *grad_out, int P, 
                                                   const float *xyz_min, const float *xyz_max, int freq_num, int64_t n,
                                                   float *grad_grid, uint32_t *touch, ugrid_stream_t s) {
   return ug_grid_query_backward_any(true, grad_out, P, C, X, Y, Z, xyz, xyz_min, xyz_max, freq_num, n, grad_grid, ST(s), touch);
+}
+
+extern "C" int ugrid_count_views_accumulate(const float *rays_o, const float *rays_d, int64_t n_rays, const float *xyz_min,
+                                            const float *xyz_max, float near, float far, float stepdist, int32_t n_samples, int X, int Y,
+                                            int Z, float *acc, ugrid_stream_t s) {
+  if (n_rays <= 0 || n_samples <= 0) return 0;
+  if (!rays_o || !rays_d || !xyz_min || !xyz_max || !acc || X < 1 || Y < 1 || Z < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_count_views_accumulate, dim3(ug_blocks(n_rays, 64)), dim3(64), 0, ST(s), rays_o, rays_d, n_rays, xyz_min, xyz_max,
+                     near, far, stepdist, n_samples, X, Y, Z, acc);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_count_views_commit(float *acc, float *count, int64_t n, ugrid_stream_t s) {
+  if (n <= 0) return 0;
+  if (!acc || !count) return (int)hipErrorInvalidValue;
+  const int64_t blocks = ug_blocks(n, 256);
+  hipLaunchKernelGGL(k_count_views_commit, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, ST(s), acc, count, n);
+  UG_LAUNCH_CHECK();
+  return 0;
 }
 
 static inline int ug_brick_ch(int C, int *H) {

@@ -7,37 +7,12 @@
 // Reference behaviour restated (never copied): FourierGrid/cuda/render_utils_kernel.cu,
 // ub360_utils_kernel.cu -- per-function file:line citations are in include/ugrid_hip.h.
 #include "ugrid_common.h"
+#include "ugrid_rays.h"
 
 extern "C" int ugrid_abi_version(void) { return 3; }  // 2: ugrid_render_params.mlp_mode, ugrid_pack_mlp(k0_absmax, best_mode); 3: ugrid_frame_metrics
 extern "C" const char *ugrid_target_arch(void) { return "gfx950"; }
 
-// ----------------------------------------------------------------------------------------------
-// Ray / AABB helpers (1 lane per ray; 12-byte AoS rays are read as 3 dwords, L1 absorbs the stride)
-// ----------------------------------------------------------------------------------------------
-struct ug_tmm { float tmin, tmax; };
-
-__device__ __forceinline__ ug_tmm ug_t_minmax(const float *o, const float *d, const float *lo,
-                                              const float *hi, float near, float far) {
-  // a zero direction component is replaced by float(1e-6) (double literal narrowed)
-  const float vx = (d[0] == 0.f) ? (float)1e-6 : d[0];
-  const float vy = (d[1] == 0.f) ? (float)1e-6 : d[1];
-  const float vz = (d[2] == 0.f) ? (float)1e-6 : d[2];
-  const float ax = (hi[0] - o[0]) / vx, ay = (hi[1] - o[1]) / vy, az = (hi[2] - o[2]) / vz;
-  const float bx = (lo[0] - o[0]) / vx, by = (lo[1] - o[1]) / vy, bz = (lo[2] - o[2]) / vz;
-  ug_tmm r;
-  r.tmin = fmaxf(fminf(fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz)), far), near);
-  r.tmax = fmaxf(fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)), far), near);
-  return r;
-}
-
-__device__ __forceinline__ float ug_norm3(const float *d) {
-  return sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-}
-
-__device__ __forceinline__ int64_t ug_n_samples(const float *d, float tmin, float tmax, float stepdist) {
-  const double c = (double)ceilf((tmax - tmin) * ug_norm3(d) / stepdist);
-  return (int64_t)(c > 1. ? c : 1.);
-}
+// Ray / AABB helpers (ug_t_minmax, ug_norm3, ug_n_samples, ug_sample_point, ug_mask_index): ugrid_rays.h
 
 __global__ void k_infer_t_minmax(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
                                  const float *__restrict__ xyz_min, const float *__restrict__ xyz_max,
@@ -182,18 +157,11 @@ __global__ void k_sample_fill(const float *__restrict__ rays_o, const float *__r
   }
   const int64_t r = lo;
   const int64_t s = idx - (r ? cumsum[r - 1] : 0);
-  const float *o = rays_o + 3 * r, *d = rays_d + 3 * r;
-  const float rn = ug_norm3(d), tm = t_min[r];
-  const float dist = stepdist * (float)(int)s;
+  const float lo_[3] = {xyz_min[0], xyz_min[1], xyz_min[2]}, hi_[3] = {xyz_max[0], xyz_max[1], xyz_max[2]};
   float p[3];
-  for (int c = 0; c < 3; ++c) {
-    const float start = o[c] + d[c] * tm;
-    const float dir = d[c] / rn;
-    p[c] = start + dir * dist;
-    rays_pts[3 * idx + c] = p[c];
-  }
-  mask_outbbox[idx] = (uint8_t)((xyz_min[0] > p[0]) | (xyz_min[1] > p[1]) | (xyz_min[2] > p[2]) |
-                                (xyz_max[0] < p[0]) | (xyz_max[1] < p[1]) | (xyz_max[2] < p[2]));
+  const bool out = ug_sample_point(rays_o + 3 * r, rays_d + 3 * r, ug_norm3(rays_d + 3 * r), t_min[r], stepdist, (int)s, lo_, hi_, p);
+  for (int c = 0; c < 3; ++c) rays_pts[3 * idx + c] = p[c];
+  mask_outbbox[idx] = (uint8_t)out;
   ray_id[idx] = r;
   step_id[idx] = s;
 }
@@ -244,18 +212,40 @@ __global__ void k_maskcache(const uint8_t *__restrict__ world, const float *__re
                             uint8_t *__restrict__ out) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
-  float fi = roundf(xyz[3 * p] * scale[0] + shift[0]);
-  float fj = roundf(xyz[3 * p + 1] * scale[1] + shift[1]);
-  float fk = roundf(xyz[3 * p + 2] * scale[2] + shift[2]);
-  // the reference converts the rounded value with `const int i = round(...)` (render_utils_kernel.cu:385-387): the
-  // hardware float->int conversion saturates and maps NaN to 0 (v_cvt_i32_f32, and cvt.rzi.s32.f32 on the
-  // reference's own target), so a NaN coordinate indexes plane 0 of that axis -- pinned on the reference kernels
-  // themselves (tests/golden/native_ops.npz); +-inf / huge values saturate out of range
-  fi = (fi != fi) ? 0.f : fi; fj = (fj != fj) ? 0.f : fj; fk = (fk != fk) ? 0.f : fk;
-  uint8_t v = 0;
-  if (fi >= 0.f && fi < (float)sz_i && fj >= 0.f && fj < (float)sz_j && fk >= 0.f && fk < (float)sz_k)
-    v = world[(int64_t)fi * sz_j * sz_k + (int64_t)fj * sz_k + (int64_t)fk];
-  out[p] = v;
+  const int64_t at = ug_mask_index(xyz + 3 * p, scale, shift, sz_i, sz_j, sz_k);      // (-1: outside the mask grid)
+  out[p] = at >= 0 ? world[at] : (uint8_t)0;
+}
+
+// hit_coarse_geo (dvgo.py:291-304) as ONE kernel, 1 lane per ray: the reference composes sample_pts_on_rays (points + ids of every
+// sample of every ray: 29 B per sample and a host read of the total), a boolean index, maskcache_lookup and a scatter.  Here a ray
+// walks its own samples -- the same t_min / step count / point / out-of-box test / mask voxel, through the same device functions as
+// k_sample_count, k_sample_fill and k_maskcache -- and stops at the first occupied cell: the same bits, no sample ever stored.
+__global__ void k_hit_coarse_geo(const float *__restrict__ rays_o, const float *__restrict__ rays_d, int64_t n_rays,
+                                 const float *__restrict__ xyz_min, const float *__restrict__ xyz_max, float near, float far,
+                                 float stepdist, const uint8_t *__restrict__ world, int64_t sz_i, int64_t sz_j, int64_t sz_k,
+                                 const float *__restrict__ scale, const float *__restrict__ shift, uint8_t *__restrict__ hit) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays) return;
+  const float lo[3] = {xyz_min[0], xyz_min[1], xyz_min[2]}, hi[3] = {xyz_max[0], xyz_max[1], xyz_max[2]};
+  const float sc[3] = {scale[0], scale[1], scale[2]}, sh[3] = {shift[0], shift[1], shift[2]};
+  const float o[3] = {rays_o[3 * r], rays_o[3 * r + 1], rays_o[3 * r + 2]}, d[3] = {rays_d[3 * r], rays_d[3 * r + 1], rays_d[3 * r + 2]};
+  const ug_tmm t = ug_t_minmax(o, d, lo, hi, near, far);
+  int64_t n = ug_n_samples(d, t.tmin, t.tmax, stepdist);
+  // a finite ray's samples span at most the box diagonal (t_min .. t_max lie on the box): like the sampling march's slots, a bound that
+  // never binds on them -- it keeps a ray of non-finite numbers, whose count saturates, from walking forever
+  const float ext[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+  const float diag_steps = ceilf(ug_norm3(ext) / stepdist);
+  const int64_t cap = (diag_steps < 2e9f ? (int64_t)diag_steps : 0) + 3;      // (a box that is not finite either: three samples)
+  if (!(n <= cap)) n = cap;
+  const float rn = ug_norm3(d);
+  uint8_t h = 0;
+  for (int64_t s = 0; s < n; ++s) {
+    float p[3];
+    if (ug_sample_point(o, d, rn, t.tmin, stepdist, (int)s, lo, hi, p)) continue;
+    const int64_t at = ug_mask_index(p, sc, sh, sz_i, sz_j, sz_k);
+    if (at >= 0 && world[at]) { h = 1; break; }
+  }
+  hit[r] = h;
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -598,6 +588,20 @@ extern "C" int ugrid_maskcache_lookup(const uint8_t *world, const float *xyz, co
   if (n_pts <= 0) return 0;
   hipLaunchKernelGGL(k_maskcache, dim3(ug_blocks(n_pts, 256)), dim3(256), 0, ST(s), world, xyz, scale,
                      shift, sz_i, sz_j, sz_k, n_pts, out);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_hit_coarse_geo(const float *rays_o, const float *rays_d, int64_t n_rays, const float *xyz_min,
+                                    const float *xyz_max, float near, float far, float stepdist, const uint8_t *mask, int64_t mi,
+                                    int64_t mj, int64_t mk, const float *xyz2ijk_scale, const float *xyz2ijk_shift, uint8_t *hit,
+                                    ugrid_stream_t s) {
+  if (n_rays <= 0) return 0;
+  if (!rays_o || !rays_d || !xyz_min || !xyz_max || !mask || !xyz2ijk_scale || !xyz2ijk_shift || !hit || mi < 1 || mj < 1 || mk < 1 ||
+      !(stepdist > 0.f))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_hit_coarse_geo, dim3(ug_blocks(n_rays, 256)), dim3(256), 0, ST(s), rays_o, rays_d, n_rays, xyz_min, xyz_max, near, far,
+                     stepdist, mask, mi, mj, mk, xyz2ijk_scale, xyz2ijk_shift, hit);
   UG_LAUNCH_CHECK();
   return 0;
 }

@@ -1,5 +1,5 @@
 // One training step of the dense-grid models (DirectVoxGO, DirectContractedVoxGO, DirectMPIGO) and of FourierGridModel issued
-// natively (include/ugrid_hip.h: ugrid_voxgo_step, modes 0-3).
+// natively (include/ugrid_hip.h: ugrid_voxgo_step, modes 0-3; colour 0 = the rgbnet on all of k0, 1 = no rgbnet, the coarse stage).
 //
 // The op-by-op step (voxgo_model.py + train_step.py) is host-bound: ~30 launches through Python + ctypes + four autograd nodes
 // take ~0.9 ms to issue for 0.8 ms of GPU time.  Nothing here is a new algorithm: the three entry points call
@@ -79,8 +79,10 @@ static ug_step_ws ug_step_layout(const ugrid_voxgo_step *s) {
   auto take = [&](int64_t n) { float *p = s->ws ? s->ws + o : nullptr; o += ug_al(n); return p; };
   w.pts1 = take(3 * M1); w.dens1 = take(M1); w.w1 = take(M1); w.T1 = take(M1);
   w.pos2 = (int32_t *)take(M1);
-  w.pts2 = take(3 * M2); w.k0 = take(M2 * s->C); w.feat = take(M2 * K); w.h1 = take(M2 * s->width); w.h2 = take(M2 * s->width);
-  w.ray_rows = take(s->n_rays * (3 + 6 * s->pe));      // the view embedding per ray (ugrid_rgbnet_features' scratch)
+  const int64_t net = s->colour == 1 ? 0 : 1;          // no rgbnet: the k0 lookup writes the logits themselves, nothing of the network is kept
+  w.pts2 = take(3 * M2); w.k0 = take(net * M2 * s->C); w.feat = take(net * M2 * K); w.h1 = take(net * M2 * s->width);
+  w.h2 = take(net * M2 * s->width);
+  w.ray_rows = take(net * s->n_rays * (3 + 6 * s->pe));      // the view embedding per ray (ugrid_rgbnet_features' scratch)
   w.total = o;
   return w;
 }
@@ -90,8 +92,9 @@ static ug_step_ws_bwd ug_step_layout_bwd(const ugrid_voxgo_step *s) {
   const int64_t M1 = s->M1, M2 = s->M2;
   int64_t o = 0;
   auto take = [&](int64_t n) { float *p = s->ws_bwd ? s->ws_bwd + o : nullptr; o += ug_al(n); return p; };
-  w.g_logits = take(3 * M2); w.g_w = take(M2); w.g_dens = take(M2); w.g_ainv = take(s->n_rays); w.g_k0 = take(M2 * s->C);
-  w.g1 = take(M1); w.rg = take(ugrid_rgbnet_train_scratch_floats(M2));
+  const bool net = s->colour != 1;                     // no rgbnet: the k0 scatter reads g_logits
+  w.g_logits = take(3 * M2); w.g_w = take(M2); w.g_dens = take(M2); w.g_ainv = take(s->n_rays); w.g_k0 = take(net ? M2 * s->C : 0);
+  w.g1 = take(M1); w.rg = take(net ? ugrid_rgbnet_train_scratch_floats(M2) : 0);
   w.total = o;
   return w;
 }
@@ -102,7 +105,7 @@ extern "C" int64_t ugrid_voxgo_step_bwd_ws_floats(const ugrid_voxgo_step *s) { r
 
 static int ug_step_check(const ugrid_voxgo_step *s) {
   if (!s || s->mode < 0 || s->mode > 3 || s->n_rays <= 0 || s->slots <= 0 || s->C < 1 || s->pe < 0 || s->P < 1 || s->kP < 1 ||
-      s->freq_num < 0 || s->k0_freq_num < 0)
+      s->freq_num < 0 || s->k0_freq_num < 0 || s->colour < 0 || s->colour > 1 || (s->colour == 1 && s->C != 3))
     return (int)hipErrorInvalidValue;
   if (s->mode != 2 && (s->P != 1 || s->freq_num != 0)) return (int)hipErrorInvalidValue;       // the dense-grid models' density grid
   if (s->P != 1 + 2 * s->freq_num && !(s->P == 1 && s->freq_num == 0)) return (int)hipErrorInvalidValue;
@@ -110,7 +113,8 @@ static int ug_step_check(const ugrid_voxgo_step *s) {
   // DirectMPIGO: one level each, the per-plane shift table the march reads, a mask cache, the s table, ugrid_train_sample_mpi's limits
   if (s->mode == 3 && (s->kP != 1 || !s->plane_shift || !s->mask || !s->t_table || s->mpi_depth < 1 || s->mpi_depth > 256 || s->slots < 2))
     return (int)hipErrorInvalidValue;
-  if (s->width < 1 || s->width > 128 || s->C + 3 + 6 * s->pe > 128) return (int)hipErrorNotSupported;
+  // (colour 1 has no network: neither its limits nor its weights -- w0 .. b2 and g_w0 .. g_b2 may be NULL)
+  if (s->colour == 0 && (s->width < 1 || s->width > 128 || s->C + 3 + 6 * s->pe > 128)) return (int)hipErrorNotSupported;
   if (s->sync_free && (s->M1 < s->n_rays * (int64_t)s->slots || s->M2 < 1 || s->M2 > s->M1 || s->hint1 < 0 || s->hint2 < 0))
     return (int)hipErrorInvalidValue;                    // capacities: stage 1 cannot overflow, stage 2 is clamped by the compaction
   return 0;
@@ -180,13 +184,16 @@ extern "C" int ugrid_voxgo_step_forward(const ugrid_voxgo_step *s, ugrid_stream_
                                         s->step_id2, s->t2, s->mode == 1 ? s->inner2 : nullptr, st);
     if (rc) return rc;
   }
+  // colour 1: the 3-channel lookup IS the logits (the coarse stage's `rgb = sigmoid(k0)`)
   rc = (s->k0_channels_last ? ugrid_grid_query_cl : ugrid_grid_query)(s->k0_grid, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min,
-                                                                     s->k0_xyz_max, s->k0_freq_num, M2, w.k0, st);
+                                                                     s->k0_xyz_max, s->k0_freq_num, M2, s->colour == 1 ? s->logits : w.k0, st);
   if (rc) return rc;
-  rc = ugrid_rgbnet_features(w.k0, s->C, s->viewdirs, R, s->viewfreq, s->pe, s->ray_id2, M2, w.ray_rows, w.feat, st);
-  if (rc) return rc;
-  rc = ugrid_rgbnet_train_forward(w.feat, M2, K, s->w0, s->b0, s->w1, s->b1, s->w2, s->b2, s->width, w.h1, w.h2, s->logits, st);
-  if (rc) return rc;
+  if (s->colour == 0) {
+    rc = ugrid_rgbnet_features(w.k0, s->C, s->viewdirs, R, s->viewfreq, s->pe, s->ray_id2, M2, w.ray_rows, w.feat, st);
+    if (rc) return rc;
+    rc = ugrid_rgbnet_train_forward(w.feat, M2, K, s->w0, s->b0, s->w1, s->b1, s->w2, s->b2, s->width, w.h1, w.h2, s->logits, st);
+    if (rc) return rc;
+  }
   return ugrid_render_loss(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9, s->seg,
                            s->rgb_marched, s->ray_tot, s->partial, s->out2, st);
 }
@@ -204,14 +211,18 @@ extern "C" int ugrid_voxgo_step_backward_k0(const ugrid_voxgo_step *s, ugrid_str
   rc = ugrid_render_loss_backward(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9,
                                   s->seg, s->rgb_marched, s->ray_tot, s->grad_loss, b.g_logits, b.g_w, b.g_ainv, b.g_dens, st);
   if (rc) return rc;
-  rc = ugrid_rgbnet_train_backward(b.g_logits, w.feat, w.h1, w.h2, M2, K, s->C, s->w0, s->w1, s->w2, s->width, b.g_k0, s->g_w0, s->g_b0,
-                                   s->g_w1, s->g_b1, s->g_w2, s->g_b2, b.rg, st);
-  if (rc) return rc;
+  const float *g_k0 = b.g_logits;                      // colour 1: the logits are the lookup's output
+  if (s->colour == 0) {
+    rc = ugrid_rgbnet_train_backward(b.g_logits, w.feat, w.h1, w.h2, M2, K, s->C, s->w0, s->w1, s->w2, s->width, b.g_k0, s->g_w0, s->g_b0,
+                                     s->g_w1, s->g_b1, s->g_w2, s->g_b2, b.rg, st);
+    if (rc) return rc;
+    g_k0 = b.g_k0;
+  }
   if (s->k0_channels_last && s->touch)
-    return ugrid_grid_query_backward_cl_touch(b.g_k0, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min, s->k0_xyz_max, s->k0_freq_num,
+    return ugrid_grid_query_backward_cl_touch(g_k0, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min, s->k0_xyz_max, s->k0_freq_num,
                                               M2, s->grad_k0_grid, s->touch, st);
   return (s->k0_channels_last ? ugrid_grid_query_backward_cl : ugrid_grid_query_backward)(
-      b.g_k0, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min, s->k0_xyz_max, s->k0_freq_num, M2, s->grad_k0_grid, st);
+      g_k0, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min, s->k0_xyz_max, s->k0_freq_num, M2, s->grad_k0_grid, st);
 }
 
 // second half: the sampling's backward and the density grid's gradient (reads what the first half left in ws_bwd)

@@ -75,6 +75,8 @@ class VoxGOStep(torch.autograd.Function):
     viewfreq [pe], t (dcvgo, fourier: the sample table [S]; mpi: the s table (j + 0.5) / n_steps, [n_steps] -- the `t` output is
     then the samples' s, and the loss takes it as both s and t), xyz_min / xyz_max, k0_xyz_min / k0_xyz_max, mask (bool [mi,mj,mk];
     none for 'fourier'), target [R,3], bg [R,3] or None, coef (ops.loss_coefficients).
+    pack['colour'] (optional) 'none': the coarse stage -- no rgbnet, the colour logits are the 3-channel k0 lookup itself (ugrid_voxgo_step.colour
+    = 1); the six weights are passed as None and get no gradient, viewdirs / viewfreq are not read.
     pack['sync_free'] (optional: True or {'capacity': rows of the stage-2 arrays (default rays x slots: cannot overflow), 'hints': (M1, M2)
     expected counts}): the step makes no host read and synchronises nothing -- forward and backward only enqueue work, the whole step can
     run ahead of the host or be captured in a hipGraph (include/ugrid_hip.h ugrid_voxgo_step.sync_free).  The per-sample outputs then
@@ -89,12 +91,15 @@ class VoxGOStep(torch.autograd.Function):
     def forward(ctx, density_grid, k0_grid, w0, b0, w1, b1, w2, b2, pack):
         cfg, mode = pack['cfg'], pack['mode']
         # (dense copies where a caller hands in views: the op-by-op ops do the same)
-        rays_o, rays_d, viewdirs = (pack[k].contiguous() for k in ('rays_o', 'rays_d', 'viewdirs'))
-        target, viewfreq = pack['target'].contiguous(), pack['viewfreq'].contiguous()
+        net = pack.get('colour') != 'none'
+        rays_o, rays_d, target = (pack[k].contiguous() for k in ('rays_o', 'rays_d', 'target'))
+        viewdirs, viewfreq = (pack[k].contiguous() for k in ('viewdirs', 'viewfreq')) if net else (None, None)
         bg = pack['bg'].contiguous() if pack.get('bg') is not None else None
-        ws_ = [x.contiguous() for x in (w0, b0, w1, b1, w2, b2)]
-        f32 = [("density grid", density_grid), ("rays_o", rays_o), ("rays_d", rays_d), ("viewdirs", viewdirs),
-               ("target", target), ("viewfreq", viewfreq)] + [("rgbnet", x) for x in ws_]
+        if not net and any(x is not None for x in (w0, b0, w1, b1, w2, b2)):
+            raise RuntimeError("VoxGOStep: colour 'none' has no rgbnet -- pass None for its six weights")
+        ws_ = [x.contiguous() for x in (w0, b0, w1, b1, w2, b2)] if net else []
+        f32 = [("density grid", density_grid), ("rays_o", rays_o), ("rays_d", rays_d), ("target", target)] \
+            + ([("viewdirs", viewdirs), ("viewfreq", viewfreq)] if net else []) + [("rgbnet", x) for x in ws_]
         if bg is not None:
             f32.append(("bg", bg))
         mask = pack.get('mask')
@@ -139,10 +144,13 @@ class VoxGOStep(torch.autograd.Function):
         R = rays_o.shape[0]
         t = t_tab
         S = int(cfg['slots']) if mode == 'dvgo' else int(cfg['n_steps']) if mode == 'mpi' else t.numel()
-        C, W, pe = k0_grid.shape[1], ws_[0].shape[0], viewfreq.numel()
-        if tuple(ws_[0].shape) != (W, C + 3 + 6 * pe) or tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W):
+        C = k0_grid.shape[1]
+        W, pe = (ws_[0].shape[0], viewfreq.numel()) if net else (0, 0)
+        if net and (tuple(ws_[0].shape) != (W, C + 3 + 6 * pe) or tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W)):
             raise RuntimeError("VoxGOStep: rgbnet weights must be [W, C+3+6pe], [W,W], [3,W]")
-        if viewdirs.shape != (R, 3) or rays_d.shape != (R, 3) or target.shape != (R, 3) or (bg is not None and bg.shape != (R, 3)):
+        if not net and C != 3:
+            raise RuntimeError("VoxGOStep: colour 'none' takes a 3-channel k0 grid (got %d channels)" % C)
+        if (net and viewdirs.shape != (R, 3)) or rays_d.shape != (R, 3) or target.shape != (R, 3) or (bg is not None and bg.shape != (R, 3)):
             raise RuntimeError("VoxGOStep: rays_o, rays_d, viewdirs, target must all be [R,3]")
         sc = _grid.scratch(dev, R * S)          # the sample ops' scratch: this node's sampling half is theirs
         counts = torch.empty(2, R, dtype=torch.int32, device=dev)
@@ -154,6 +162,7 @@ class VoxGOStep(torch.autograd.Function):
         s = _lib.VoxgoStep()
         s.mode = {'dvgo': 0, 'dcvgo': 1, 'fourier': 2, 'mpi': 3}[mode]
         s.k0_channels_last = int(k0_cl)
+        s.colour = 0 if net else 1
         s.P, s.kP = density_grid.shape[0], k0_grid.shape[0]
         s.freq_num, s.k0_freq_num = (max(int(cfg['freq_num']), 0), max(int(cfg['k0_freq_num']), 0)) if mode == 'fourier' else (0, 0)
         s.X, s.Y, s.Z = density_grid.shape[2:]
@@ -181,10 +190,11 @@ class VoxGOStep(torch.autograd.Function):
         s.density_grid, s.k0_grid = density_grid.data_ptr(), k0_grid.data_ptr()
         s.xyz_min, s.xyz_max = box['xyz_min'].data_ptr(), box['xyz_max'].data_ptr()
         s.k0_xyz_min, s.k0_xyz_max = box['k0_xyz_min'].data_ptr(), box['k0_xyz_max'].data_ptr()
-        s.viewfreq = viewfreq.data_ptr()
+        if net:
+            s.viewfreq, s.viewdirs = viewfreq.data_ptr(), viewdirs.data_ptr()
         for n, x in zip(_WEIGHTS, ws_):
             setattr(s, n, x.data_ptr())
-        s.rays_o, s.rays_d, s.viewdirs, s.target = rays_o.data_ptr(), rays_d.data_ptr(), viewdirs.data_ptr(), target.data_ptr()
+        s.rays_o, s.rays_d, s.target = rays_o.data_ptr(), rays_d.data_ptr(), target.data_ptr()
         s.bg = bg.data_ptr() if bg is not None else None
         s.sc_pts, s.sc_density, s.sc_step, s.sc_w, s.sc_T = (x.data_ptr() for x in sc)
         s.counts, s.offsets = counts.data_ptr(), i64.data_ptr()
@@ -267,6 +277,8 @@ class VoxGOStep(torch.autograd.Function):
             ready = None       # a gradient is already accumulated on the k0 grid: this one has to be ADDED by autograd, not consumed here
         with _lib.guard(dev):
             st = _lib.stream_of(g_loss)
+            if not gw:
+                gw = [None] * len(_WEIGHTS)          # colour 'none': no rgbnet, no gradients for it
             if ready is None:
                 _lib.check(_L.ugrid_voxgo_step_backward(ps, st), "voxgo_step_backward")
                 return (g_density, g_k0, *gw, None)

@@ -36,6 +36,9 @@ class TrainModel(nn.Module):
     fourier_freq_num = 0
     splitk_rgbnet = False       # ops.SplitKLinear weight gradients where ops.FusedRgbnet does not apply (FourierGridModel)
     table_end = None            # contracted models: the sample table's inner samples span [0, table_end]
+    native_coarse = False       # True: the coarse stage (no rgbnet, 3-channel k0) of DirectVoxGO / DirectContractedVoxGO also takes
+                                # native_step.VoxGOStep (colour 'none'); the other models ignore it
+    _native_coarse_ok = False   # (the models whose forward passes the colour mode on)
 
     # -- construction helpers ------------------------------------------------------------------------------
     def _make_grid(self, channels, world_size, fourier, channels_last):
@@ -128,15 +131,24 @@ class TrainModel(nn.Module):
         """The parameters of native_step.VoxGOStep (density grid, k0 grid, the rgbnet's three weights and biases), or None when this
         configuration takes the op-by-op ops: the native step needs the default 3-layer rgbnet fed by all of k0 (rgbnet_direct, where
         the model has the choice), gradients on, every one of those parameters trainable, and both grids looked up by the HIP kernels
-        (no injected query function) with the levels they were built with."""
-        if not (self.native_step and self.fused_rgbnet and self.rgbnet is not None and torch.is_grad_enabled()
-                and getattr(self, 'rgbnet_direct', True)):
+        (no injected query function) with the levels they were built with.
+        The coarse stage -- no rgbnet, the colour is the 3-channel k0 itself -- takes the native step only where `native_coarse` asks
+        for it: the two grids followed by six None (VoxGOStep colour 'none')."""
+        if not (self.native_step and torch.is_grad_enabled()):
             return None
-        lin = _ops.rgbnet_linears(self.rgbnet)
-        if lin is None:
-            return None
-        params = [self.density.grid, self.k0.grid] + [p for l in lin for p in (l.weight, l.bias)]
-        if not all(p.requires_grad for p in params) \
+        if self.rgbnet is None:
+            if not (self.native_coarse and self._native_coarse_ok and self.k0.grid.shape[1] == 3):
+                return None
+            nets = [None] * 6
+        else:
+            if not (self.fused_rgbnet and getattr(self, 'rgbnet_direct', True)):
+                return None
+            lin = _ops.rgbnet_linears(self.rgbnet)
+            if lin is None:
+                return None
+            nets = [p for l in lin for p in (l.weight, l.bias)]
+        params = [self.density.grid, self.k0.grid] + nets
+        if not all(p.requires_grad for p in params if p is not None) \
                 or any(g.query_fn is not None or g.grid.shape[0] != 1 + 2 * max(g.nerf_pos_num_freq, 0) for g in (self.density, self.k0)):
             return None
         return params
@@ -145,7 +157,8 @@ class TrainModel(nn.Module):
         """The training forward + loss as ONE autograd node issued from C (native_step.VoxGOStep): the same kernels, sizes and order
         as the op-by-op ops; the reference's return dict with loss / mse added, the per-sample arrays detached"""
         from .native_step import VoxGOStep
-        pack = {'mode': mode, 'cfg': cfg, 't': t, 'rays_o': rays_o, 'rays_d': rays_d, 'viewdirs': viewdirs, 'viewfreq': self.viewfreq,
+        pack = {'mode': mode, 'cfg': cfg, 't': t, 'rays_o': rays_o, 'rays_d': rays_d, 'viewdirs': viewdirs,
+                'viewfreq': self.viewfreq if self.rgbnet is not None else None, 'colour': 'none' if self.rgbnet is None else 'rgbnet',
                 'xyz_min': self.xyz_min, 'xyz_max': self.xyz_max, 'k0_xyz_min': self.k0.xyz_min, 'k0_xyz_max': self.k0.xyz_max,
                 'mask': mask, 'target': fused_loss['target'], 'bg': bg, 'coef': fused_loss['coef'], 'sync_free': self.native_sync_free}
         loss, mse = VoxGOStep.apply(*params, pack)

@@ -13,13 +13,17 @@ the 288 GB, so the ray table stays resident and a batch is four device-side row 
 NDC (forward-facing) ray tables -- cfg.data.ndc, the DirectMPIGO path (mpi_model.py) -- come from the functions of their own,
 `get_training_rays_ndc` / `get_training_rays_flatten_ndc`; the four functions above refuse ndc=True.
 
-Also the two ray-preparation utilities the models and DirectVoxGORenderer share, `voxel_count_views` and `hit_coarse_geo`."""
+Also the two ray-preparation utilities the models and DirectVoxGORenderer share, `voxel_count_views` and `hit_coarse_geo`: on the
+package's own ops and float32 device rays each is a kernel of its own per image (ugrid_count_views_accumulate / _commit,
+ugrid_hit_coarse_geo: no materialised samples, no autograd, no host read); FUSED_SETUP = False, an injected back-end or CPU
+tensors take the composed paths."""
 import numpy as np
 import torch
 
 from .fourier_render import get_rays_of_a_view
 
 FOURIERGRID_DATASETS = ("waymo", "mega", "nerfpp")      # FourierGrid_model.py:307
+FUSED_SETUP = True      # voxel_count_views / hit_coarse_geo on their fused kernels where they apply (False: the composed paths, the A/B)
 
 
 _NDC = object()
@@ -187,15 +191,63 @@ def sample_batch(cfg_train, rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr, indexs_tr
     return tuple(out)
 
 
+def _fused_rays(*rays):
+    """the fused set-up kernels take float32 rays that live on the GPU"""
+    return FUSED_SETUP and all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 for x in rays)
+
+
+def _count_n_samples(world_size, stepsize):
+    return int(np.linalg.norm(world_size.cpu().numpy().astype(np.float64) + 1) / stepsize) + 1
+
+
+@torch.no_grad()
+def voxel_count_views_fused(xyz_min, xyz_max, voxel_size, world_size, count_shape, rays_o_tr, rays_d_tr, imsz, near, stepsize,
+                            downrate=1, irregular_shape=False):
+    """voxel_count_views on two kernels per image (ugrid_count_views_accumulate: one lane per ray adds the trilinear footprint of its
+    samples into a scratch grid; ugrid_count_views_commit: count += scratch > 1, scratch = 0): the whole image at once, no points
+    materialised, no autograd, no host read.  Same images ([::downrate, ::downrate] / the imsz split), same n_samples, and
+    stepdist = stepsize * voxel_size formed in float32 like the composed path's; the same sums in another order."""
+    from . import _lib
+    L = _lib.load()
+    dev = xyz_min.device
+    far = 1e9
+    n_samples = _count_n_samples(world_size, stepsize)
+    stepdist = float(stepsize * voxel_size)                  # (the float32 product of the composed path, read back once)
+    X, Y, Z = (int(x) for x in world_size.tolist())
+    lo, hi = xyz_min.contiguous(), xyz_max.contiguous()
+    _lib.require_cuda(("xyz_min", lo), ("xyz_max", hi))
+    _lib.require_f32(("xyz_min", lo), ("xyz_max", hi))
+    count = torch.zeros(count_shape, device=dev)
+    if count.numel() != X * Y * Z:
+        raise RuntimeError("voxel_count_views: count_shape %s does not hold world_size %s" % (tuple(count_shape), (X, Y, Z)))
+    acc = torch.zeros(X * Y * Z, device=dev)
+    with _lib.guard(dev):
+        st = _lib.stream_of(count)
+        for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
+            if not irregular_shape:
+                o_img, d_img = o_img[::downrate, ::downrate], d_img[::downrate, ::downrate]
+            o, d = o_img.to(dev).reshape(-1, 3).contiguous(), d_img.to(dev).reshape(-1, 3).contiguous()
+            _lib.check(L.ugrid_count_views_accumulate(o.data_ptr(), d.data_ptr(), o.shape[0], lo.data_ptr(), hi.data_ptr(), float(near), far,
+                                                      stepdist, n_samples, X, Y, Z, acc.data_ptr(), st), "count_views_accumulate")
+            _lib.check(L.ugrid_count_views_commit(acc.data_ptr(), count.data_ptr(), X * Y * Z, st), "count_views_commit")
+    return count
+
+
 def voxel_count_views(query, xyz_min, xyz_max, voxel_size, world_size, count_shape, rays_o_tr, rays_d_tr, imsz, near, stepsize,
                       downrate=1, irregular_shape=False):
     """How many training views see each voxel of a plain grid of `world_size` over the box (dvgo.py:247-277,
     FourierGrid_model.py:392-418): per image the trilinear footprint of its rays' samples is scattered into a zero grid -- by
     the backward of `query`, a differentiable lookup (grid.GridQuery.apply or an injected one) -- and a voxel counts as seen
-    when it gathered more than 1.  Returns the counts as a float grid of `count_shape` (the model's density grid's)."""
+    when it gathered more than 1.  Returns the counts as a float grid of `count_shape` (the model's density grid's).
+    With the package's own lookup and float32 rays on the GPU: voxel_count_views_fused."""
+    from . import grid as _grid
+    # (`==`: every access of a Function's `apply` makes a new bound method; equal ones are the same op)
+    if query == _grid.GridQuery.apply and _fused_rays(rays_o_tr, rays_d_tr) and xyz_min.is_cuda:
+        return voxel_count_views_fused(xyz_min, xyz_max, voxel_size, world_size, count_shape, rays_o_tr, rays_d_tr, imsz, near, stepsize,
+                                       downrate, irregular_shape)
     far = 1e9
     dev = xyz_min.device
-    n_samples = int(np.linalg.norm(world_size.cpu().numpy().astype(np.float64) + 1) / stepsize) + 1
+    n_samples = _count_n_samples(world_size, stepsize)
     rng = torch.arange(n_samples, device=dev)[None].float()
     count = torch.zeros(count_shape, device=dev)
     for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
@@ -220,10 +272,28 @@ def voxel_count_views(query, xyz_min, xyz_max, voxel_size, world_size, count_sha
 @torch.no_grad()
 def hit_coarse_geo(ru, rays_o, rays_d, xyz_min, xyz_max, near, stepdist, mask, xyz2ijk_scale, xyz2ijk_shift):
     """bool [...]: does the ray pass through a cell the mask cache marks as possibly occupied? (dvgo.py:291-304)
-    ru: the render_utils_cuda module (sample_pts_on_rays, maskcache_lookup) or another implementation of it."""
+    ru: the render_utils_cuda module (sample_pts_on_rays, maskcache_lookup) or another implementation of it.
+    The package's own module on float32 device rays: ONE kernel, a lane per ray (ugrid_hit_coarse_geo) -- the same bits."""
     far = 1e9
     shape = rays_o.shape[:-1]
     o, d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+    from . import render_utils_cuda as _own
+    if ru is _own and _fused_rays(o, d):
+        from . import _lib
+        small = [xyz_min.contiguous(), xyz_max.contiguous(), xyz2ijk_scale.contiguous(), xyz2ijk_shift.contiguous()]
+        named = list(zip(("xyz_min", "xyz_max", "xyz2ijk_scale", "xyz2ijk_shift"), small))
+        _lib.require_cuda(*named, ("mask", mask))
+        _lib.require_f32(*named)
+        if mask.dtype != torch.bool or mask.dim() != 3 or any(x.device != o.device for x in small + [mask]):
+            raise RuntimeError("hit_coarse_geo: mask must be a bool tensor [mi,mj,mk] on the rays' device, like the box and the scale / shift")
+        mask = mask.contiguous()
+        hit = torch.empty(o.shape[0], dtype=torch.bool, device=o.device)
+        with _lib.guard(o.device):
+            _lib.check(_lib.load().ugrid_hit_coarse_geo(o.data_ptr(), d.data_ptr(), o.shape[0], small[0].data_ptr(), small[1].data_ptr(),
+                                                        float(near), far, float(stepdist), mask.data_ptr(), *mask.shape,
+                                                        small[2].data_ptr(), small[3].data_ptr(), hit.data_ptr(), _lib.stream_of(o)),
+                       "hit_coarse_geo")
+        return hit.reshape(shape)
     pts, outbbox, ray_id = ru.sample_pts_on_rays(o, d, xyz_min, xyz_max, near, far, stepdist)[:3]
     inb = ~outbbox
     occ = ru.maskcache_lookup(mask, pts[inb].contiguous(), xyz2ijk_scale, xyz2ijk_shift)

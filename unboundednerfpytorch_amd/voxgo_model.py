@@ -35,6 +35,7 @@ class _VoxGOBase(TrainModel):
     native_sync_free = False    # True / {'capacity': rows}: that node without its host read (capacity-sized per-sample arrays, counts
                                 # on the device; native_step.VoxGOStep pack['sync_free'])
                                 # (same kernels, same bits; default rgbnet, rgbnet_direct, train_iteration's fused_loss)
+                                # (TrainModel.native_coarse = True: the coarse stage -- rgbnet_dim = 0 -- of the two models below too)
 
     def _init_grids(self, density_type, k0_type, density_config, k0_config, k0_dim, channels_last):
         if density_type != 'DenseGrid' or k0_type != 'DenseGrid':
@@ -114,6 +115,7 @@ class _VoxGOBase(TrainModel):
 
 class DirectVoxGO(_VoxGOBase):
     """The bounded model (dvgo.py:26-425)."""
+    _native_coarse_ok = True
     fused_loss = True           # train_step.train_iteration: compositing + loss as ops.RenderLoss (no distortion / nearclip term)
 
     def sample_table(self, stepsize, device):
@@ -185,7 +187,8 @@ class DirectVoxGO(_VoxGOBase):
         from . import render_utils_cuda
         from .train_rays import hit_coarse_geo
         mc = self.mask_cache
-        return hit_coarse_geo(render_utils_cuda, rays_o, rays_d, self.xyz_min, self.xyz_max, near, stepsize * self.voxel_size, mc.mask,
+        # (stepsize * voxel_size as the float32 product, read back once per resolution instead of once per image)
+        return hit_coarse_geo(render_utils_cuda, rays_o, rays_d, self.xyz_min, self.xyz_max, near, self._step_consts(stepsize)[1], mc.mask,
                               mc.xyz2ijk_scale, mc.xyz2ijk_shift)
 
     def sample_ray(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
@@ -255,6 +258,7 @@ class DirectVoxGO(_VoxGOBase):
 class DirectContractedVoxGO(_VoxGOBase):
     """The contracted-unbounded model (dcvgo.py:27-384)."""
     table_end = 2.0             # sample_ray's inner samples span [0, 2] (dcvgo.py:243-250)
+    _native_coarse_ok = True
     fused_loss = True           # train_step.train_iteration: compositing + loss as ops.RenderLoss (the losses of run_train.py:254-279)
 
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None, mask_cache_world_size=None,
