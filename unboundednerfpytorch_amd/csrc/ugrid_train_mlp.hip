@@ -695,8 +695,11 @@ k_wgrad_b3(const float *__restrict__ dY, int ldd, int n_out, const float *__rest
   }
 }
 
-// Y[s][c] = (G[s][c] > 0) ? sum_{j < K} X[s][j] * W[j][c] : 0 for K <= 4 (the gradient of the 3-channel logits pushed through the
-// last layer): three FMAs per element, one float4 of outputs per lane -- no matrix pipe needed
+// Y[s][c] = (G[s][c] > 0) ? sum_{j < K} X[s][j] * W[j][c] : 0 for K <= 4: a few FMAs per element, one float4 of outputs per lane -- no
+// matrix pipe needed.  Written for the gradient of the 3-channel logits pushed through the last layer; k_l3_bwd has taken that product
+// over wherever this kernel's own conditions hold (n_out % 4 == 0, aligned W / Y / G imply ug_l3_ok), so what still reaches it through
+// the C ABI is a net of width <= 4: dH1 = dH2 . W2 at width 4 (masked), and the input gradient at width <= 4 with
+// n_feat_grad = mlp_in a multiple of 4 (no mask) -- the cells 7/4/0 and 8/4/8 of tests/rgbnet_cases.py.
 __global__ void __launch_bounds__(256)
 k_lin_smallk(const float *__restrict__ X, int64_t M, int K, const float *__restrict__ W, int n_out, const float *__restrict__ G,
              float *__restrict__ Y, const int64_t *__restrict__ n_dev) {
