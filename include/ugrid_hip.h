@@ -290,6 +290,21 @@ int ugrid_rgbnet_train_backward(const float *g_logits, const float *feat, const 
 int ugrid_rgbnet_features(const float *k0, int32_t n_k0, const float *viewdirs, int64_t n_rays, const float *viewfreq, int32_t pe,
                           const int64_t *ray_id, int64_t m, float *ray_rows, float *out, ugrid_stream_t stream);
 
+/* The residual-colour rgbnet of the reference's DirectVoxGO with rgbnet_direct = False (dvgo.py:384-398):
+ * rgb = sigmoid(rgbnet([k0[:, 3:] | view embedding]) + k0[:, :3]).  Three elementwise leaves, one launch each, placed around
+ * ugrid_rgbnet_train_forward / _backward; k0 [m, C] is the row-major k0 lookup, C >= 4.
+ *   ugrid_rgbnet_features_residual  out [m, C - 3 + 3 + 6 pe] = [k0[:, 3:] | viewdir | sin | cos]: the values and the two launch
+ *                                   variants of ugrid_rgbnet_features on k0[:, 3:].contiguous(), read in place (row stride C).
+ *   ugrid_residual_logits           logits[i, c] += k0[i, c] for c < 3 (logits [m, 3], the rgbnet's output): one fp32 add.
+ *   ugrid_residual_k0_grad          g_k0 [m, C] = [g_logits [m, 3] | g_feat [m, C - 3]]: the gradient of the lookup, from the
+ *                                   logits' gradient and the rgbnet's input gradient (ugrid_rgbnet_train_backward with
+ *                                   n_feat_grad = C - 3).
+ * C < 4, a negative count or a NULL pointer with m > 0: hipErrorInvalidValue.  m == 0: returns 0, nothing is launched. */
+int ugrid_rgbnet_features_residual(const float *k0, int32_t C, const float *viewdirs, int64_t n_rays, const float *viewfreq, int32_t pe,
+                                   const int64_t *ray_id, int64_t m, float *ray_rows, float *out, ugrid_stream_t stream);
+int ugrid_residual_logits(float *logits, const float *k0, int32_t C, int64_t m, ugrid_stream_t stream);
+int ugrid_residual_k0_grad(const float *g_logits, const float *g_feat, int32_t C, int64_t m, float *g_k0, ugrid_stream_t stream);
+
 /* NEW (no reference counterpart; training tail): sigmoid + per-ray compositing + the loss of run_train.py:254-279 in
  * one pass, and its derivative -- replaces FourierGrid_model.py:636-647 (sigmoid, weights * rgb, segment_coo, background)
  * and run_train.py:254-279 (mse_loss, entropy_last, nearclip, flatten_eff_distloss, rgbper): ~45 + ~90 launches of the
@@ -579,6 +594,10 @@ int ugrid_train_sample_compact_vox(int64_t n_rays, int32_t slots_per_ray, float 
  *                              lookup's scatter into grad_k0_grid (+ touch bitmap when given: channel-last only), and
  *                              ugrid_train_sample_backward + the density scatter into grad_density_grid.  Both grid gradients
  *                              are ADDED to (the caller passes zeros for a fresh gradient).  ws_bwd: ugrid_voxgo_step_bwd_ws_floats.
+ * colour = 2, the residual rgbnet of DirectVoxGO (rgbnet_direct = False, dvgo.py:384-398; mode 0 is its user, no mode refuses it):
+ *   the forward runs ugrid_rgbnet_features_residual in place of ugrid_rgbnet_features, the rgbnet on mlp_in = C + 6 pe columns and
+ *   ugrid_residual_logits behind it; the backward runs the rgbnet with n_feat_grad = C - 3 and ugrid_residual_k0_grad before the
+ *   k0 scatter -- one launch more than colour 0 in each direction, the density half unchanged.
  * sync_free = 1 (round 6): the step makes NO host read and synchronises nothing -- every call only enqueues work on `stream`, so
  *   a whole step can run ahead of the host or be captured in a hipGraph.  The caller sets M1 / M2 to the CAPACITY of the per-sample
  *   arrays before ugrid_voxgo_step_sample (M1 >= n_rays * slots: the stage-1 arrays cannot overflow; M2 <= M1: stage-2 samples
@@ -633,7 +652,15 @@ typedef struct ugrid_voxgo_step {
   int32_t sync_free;        /* 1: no host read anywhere in the step (below) */
   int32_t colour;           /* 0: the rgbnet on all of k0; 1: no rgbnet (the coarse stage) -- C == 3, the k0 lookup writes `logits` itself
                                and its scatter reads their gradient; w0 .. b2, g_w0 .. g_b2, viewdirs, viewfreq may be NULL, pe / width
-                               are not looked at and the workspaces hold nothing for the network.  Anything else: hipErrorInvalidValue */
+                               are not looked at and the workspaces hold nothing for the network.
+                               2: the residual rgbnet (DirectVoxGO with rgbnet_direct = False) -- C >= 4, 1 <= width <= 128,
+                               C + 6 pe <= 128, w0 [width, K] with K = C + 6 pe; logits = rgbnet([k0[:, 3:] | embedding]) + k0[:, :3].
+                               Workspaces, with al(n) = n rounded up to 64 floats and E = 3 + 6 pe:
+                                 ws     = al(3 M1) + 4 al(M1) + al(3 M2) + al(M2 C) + al(M2 K) + 2 al(M2 width) + al(n_rays E)
+                                          (colour 0's with the rgbnet's input K columns wide instead of C + E)
+                                 ws_bwd = al(3 M2) + 2 al(M2) + al(n_rays) + al(M2 C) + al(M1) + al(ugrid_rgbnet_train_scratch_floats(M2))
+                                          + al(M2 (C - 3))   (colour 0's + the rgbnet's input gradient, kept apart from g_k0)
+                               Anything else: hipErrorInvalidValue */
   float *ws;
   float *density2, *alpha2, *weights2, *t2; /* [M2] */
   int64_t *ray_id2, *step_id2;              /* [M2] */

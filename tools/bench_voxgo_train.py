@@ -11,6 +11,9 @@ voxgo_model + train_step.train_iteration (the loop body of run_train.py:185-296)
          the COARSE stage of the same config (configs/default.py coarse_*: num_voxels 1 024 000 = 100^3, 3-channel k0 and no rgbnet,
          N_rand 8192, fast_color_thres 1e-7, entropy_last 1e-2, rgbper 1e-1, no TV, all-true mask cache; cameras on a sphere of radius 4,
          near / far 2 / 6) -- --native 1 sets native_coarse (native_step.VoxGOStep colour 'none'), 0 is the op-by-op step
+    python tools/bench_voxgo_train.py --model dvgo --residual 1 --native 0|1
+         the lego fine stage with the residual-colour rgbnet (rgbnet_direct = False, rgbnet_dim 12: the network on k0[:, 3:], its output
+         added to k0[:, :3]) -- --native 1 sets native_residual (native_step.VoxGOStep colour 'residual'), 0 is the op-by-op step
 
 One JSON line per (model, TV phase): ms per step (host clock around the timed steps, all streams), survivors, rays / s.
 Synthetic trained-like fields (bench.make_state_surfaces: smooth occupancy with opaque surfaces), random rays; `--fused 0`
@@ -53,7 +56,7 @@ def coarse_rays(n, device, seed):
     return o.contiguous(), v.clone(), v.contiguous(), rgb
 
 
-def make_model(kind, G, dev, fused, coarse=False):
+def make_model(kind, G, dev, fused, coarse=False, residual=False):
     import bench
     from unboundednerfpytorch_amd import voxgo_model as vm
     if coarse:
@@ -61,7 +64,7 @@ def make_model(kind, G, dev, fused, coarse=False):
                            fast_color_thres=1e-7, rgbnet_dim=0).to(dev)
     elif kind == "dvgo":
         m = vm.DirectVoxGO(xyz_min=[-1, -1, -1], xyz_max=[1, 1, 1], num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-2,
-                           fast_color_thres=1e-4, rgbnet_dim=12, rgbnet_direct=True).to(dev)
+                           fast_color_thres=1e-4, rgbnet_dim=12, rgbnet_direct=not residual).to(dev)
     else:
         m = vm.DirectContractedVoxGO(xyz_min=[-1, -1, -1], xyz_max=[1, 1, 1], num_voxels=G ** 3, num_voxels_base=G ** 3, alpha_init=1e-4,
                                      fast_color_thres=1e-4, rgbnet_dim=12).to(dev)
@@ -91,11 +94,15 @@ def run(kind, args, first_step):
     coarse = getattr(args, "stage", "fine") == "coarse"
     if coarse and kind != "dvgo":
         raise SystemExit("--stage coarse: the bounded model only (--model dvgo)")
+    residual = bool(getattr(args, "residual", 0))
+    if residual and (coarse or kind != "dvgo"):
+        raise SystemExit("--residual 1: the fine stage of the bounded model only (--model dvgo)")
     cfg = COARSE_CFG if coarse else CFG[kind]
     G = args.grid or (100 if coarse else 160 if kind == "dvgo" else 320)
-    m = make_model(kind, G, dev, args.fused, coarse)
+    m = make_model(kind, G, dev, args.fused, coarse, residual)
     m.native_step = bool(getattr(args, "native", 1))
     m.native_coarse = coarse and m.native_step
+    m.native_residual = residual and m.native_step
     m.native_sync_free = bool(getattr(args, "sync_free", 0))
     opt = create_optimizer_or_freeze_model(m, cfg, global_step=0)
     rk = dict(stepsize=0.5, bg=1, near=0.2, far=6.0) if kind == "dvgo" else dict(stepsize=0.5, bg=1, rand_bkgd=True)
@@ -131,9 +138,10 @@ def run(kind, args, first_step):
     tv_on = cfg["weight_tv_k0"] > 0
     return {"model": kind, "workload": "%s train step: G=%s, C=%d, %d random rays, stepsize 0.5%s" % (
                 "DirectVoxGO (lego coarse-stage shape, no rgbnet)" if coarse else
+                "DirectVoxGO (lego fine-stage shape, residual rgbnet)" if residual else
                 "DirectVoxGO (lego fine-stage shape)" if kind == "dvgo" else "DirectContractedVoxGO (mip-360 fine-stage shape)",
                 m.world_size.tolist(), m.k0.grid.shape[1], n, "" if not tv_on else ", TV " + ("dense" if first_step < cfg["tv_dense_before"] else "masked")),
-            "fused": bool(args.fused), "native_step": bool(m.native_step and args.fused and (m.native_coarse or not coarse)), "sync_free": bool(m.native_sync_free), "lazy_loss": bool(args.lazy_loss), "ms_per_step": ms, "block_ms": [round(x, 4) for x in block_ms] if n_blocks > 1 else None, "rays_per_sec": n / (ms * 1e-3), "survivors_M": int(out["weights"].numel()),
+            "fused": bool(args.fused), "native_step": bool(m.native_step and args.fused and (m.native_coarse or not coarse) and (m.native_residual or not residual)), "sync_free": bool(m.native_sync_free), "lazy_loss": bool(args.lazy_loss), "ms_per_step": ms, "block_ms": [round(x, 4) for x in block_ms] if n_blocks > 1 else None, "rays_per_sec": n / (ms * 1e-3), "survivors_M": int(out["weights"].numel()),
             "mask_cache_occupied_frac": float(m.mask_cache.mask.float().mean()), "steps": args.steps, "loss": float(loss), "psnr": float(psnr)}
 
 
@@ -149,6 +157,8 @@ def main():
                     "native_step.VoxGOStep (one node, three C calls) -- the same kernels and bits")
     ap.add_argument("--stage", default="fine", help="fine | coarse: the coarse stage of the bounded model's config (3-channel k0, no rgbnet, "
                     "100^3, fast_color_thres 1e-7); with --native 1 through native_coarse, with --native 0 op by op")
+    ap.add_argument("--residual", type=int, default=0, help="1: the bounded model's fine stage with the residual-colour rgbnet (rgbnet_direct = "
+                    "False, rgbnet_dim 12); with --native 1 through native_residual, with --native 0 op by op")
     ap.add_argument("--phase", default="both", help="dcvgo: dense | masked | both TV phases")
     ap.add_argument("--lazy-loss", type=int, default=0, help="train_iteration(return_tensors=True): no host read of loss / psnr per step "
                     "(the reference reads psnr.item() every step; a caller that logs every N steps need not)")

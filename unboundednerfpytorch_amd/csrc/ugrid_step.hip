@@ -1,5 +1,6 @@
 // One training step of the dense-grid models (DirectVoxGO, DirectContractedVoxGO, DirectMPIGO) and of FourierGridModel issued
-// natively (include/ugrid_hip.h: ugrid_voxgo_step, modes 0-3; colour 0 = the rgbnet on all of k0, 1 = no rgbnet, the coarse stage).
+// natively (include/ugrid_hip.h: ugrid_voxgo_step, modes 0-3; colour 0 = the rgbnet on all of k0, 1 = no rgbnet, the coarse stage,
+// 2 = the residual rgbnet: the network on k0[:, 3:], its output added to k0[:, :3]).
 //
 // The op-by-op step (voxgo_model.py + train_step.py) is host-bound: ~30 launches through Python + ctypes + four autograd nodes
 // take ~0.9 ms to issue for 0.8 ms of GPU time.  Nothing here is a new algorithm: the three entry points call
@@ -68,13 +69,16 @@ struct ug_step_ws {      // forward workspace: what the backward needs again, an
   int64_t total;
 };
 struct ug_step_ws_bwd {
-  float *g_logits, *g_w, *g_dens, *g_ainv, *g_k0, *g1, *rg;
+  float *g_logits, *g_w, *g_dens, *g_ainv, *g_k0, *g1, *rg, *g_feat;
   int64_t total;
 };
 
+// columns of the rgbnet's input: all of k0, or (colour 2) the channels behind the three diffuse ones, + the view embedding
+static inline int ug_step_mlp_in(const ugrid_voxgo_step *s) { return s->C - (s->colour == 2 ? 3 : 0) + 3 + 6 * s->pe; }
+
 static ug_step_ws ug_step_layout(const ugrid_voxgo_step *s) {
   ug_step_ws w;
-  const int64_t M1 = s->M1, M2 = s->M2, K = s->C + 3 + 6 * s->pe;
+  const int64_t M1 = s->M1, M2 = s->M2, K = ug_step_mlp_in(s);
   int64_t o = 0;
   auto take = [&](int64_t n) { float *p = s->ws ? s->ws + o : nullptr; o += ug_al(n); return p; };
   w.pts1 = take(3 * M1); w.dens1 = take(M1); w.w1 = take(M1); w.T1 = take(M1);
@@ -95,6 +99,7 @@ static ug_step_ws_bwd ug_step_layout_bwd(const ugrid_voxgo_step *s) {
   const bool net = s->colour != 1;                     // no rgbnet: the k0 scatter reads g_logits
   w.g_logits = take(3 * M2); w.g_w = take(M2); w.g_dens = take(M2); w.g_ainv = take(s->n_rays); w.g_k0 = take(net ? M2 * s->C : 0);
   w.g1 = take(M1); w.rg = take(net ? ugrid_rgbnet_train_scratch_floats(M2) : 0);
+  w.g_feat = take(s->colour == 2 ? M2 * (s->C - 3) : 0);      // the rgbnet's input gradient, before it joins g_logits in g_k0
   w.total = o;
   return w;
 }
@@ -105,7 +110,8 @@ extern "C" int64_t ugrid_voxgo_step_bwd_ws_floats(const ugrid_voxgo_step *s) { r
 
 static int ug_step_check(const ugrid_voxgo_step *s) {
   if (!s || s->mode < 0 || s->mode > 3 || s->n_rays <= 0 || s->slots <= 0 || s->C < 1 || s->pe < 0 || s->P < 1 || s->kP < 1 ||
-      s->freq_num < 0 || s->k0_freq_num < 0 || s->colour < 0 || s->colour > 1 || (s->colour == 1 && s->C != 3))
+      s->freq_num < 0 || s->k0_freq_num < 0 || s->colour < 0 || s->colour > 2 || (s->colour == 1 && s->C != 3) ||
+      (s->colour == 2 && s->C < 4))
     return (int)hipErrorInvalidValue;
   if (s->mode != 2 && (s->P != 1 || s->freq_num != 0)) return (int)hipErrorInvalidValue;       // the dense-grid models' density grid
   if (s->P != 1 + 2 * s->freq_num && !(s->P == 1 && s->freq_num == 0)) return (int)hipErrorInvalidValue;
@@ -114,7 +120,7 @@ static int ug_step_check(const ugrid_voxgo_step *s) {
   if (s->mode == 3 && (s->kP != 1 || !s->plane_shift || !s->mask || !s->t_table || s->mpi_depth < 1 || s->mpi_depth > 256 || s->slots < 2))
     return (int)hipErrorInvalidValue;
   // (colour 1 has no network: neither its limits nor its weights -- w0 .. b2 and g_w0 .. g_b2 may be NULL)
-  if (s->colour == 0 && (s->width < 1 || s->width > 128 || s->C + 3 + 6 * s->pe > 128)) return (int)hipErrorNotSupported;
+  if (s->colour != 1 && (s->width < 1 || s->width > 128 || ug_step_mlp_in(s) > 128)) return (int)hipErrorNotSupported;
   if (s->sync_free && (s->M1 < s->n_rays * (int64_t)s->slots || s->M2 < 1 || s->M2 > s->M1 || s->hint1 < 0 || s->hint2 < 0))
     return (int)hipErrorInvalidValue;                    // capacities: stage 1 cannot overflow, stage 2 is clamped by the compaction
   return 0;
@@ -168,7 +174,7 @@ extern "C" int ugrid_voxgo_step_forward(const ugrid_voxgo_step *s, ugrid_stream_
   if (s->M1 < 0 || s->M2 < 0 || s->M2 > s->M1 || ((s->M1 | s->M2) && !s->ws)) return (int)hipErrorInvalidValue;
   const ug_step_ws w = ug_step_layout(s);
   const int64_t R = s->n_rays, M2 = s->M2;
-  const int K = s->C + 3 + 6 * s->pe;
+  const int K = ug_step_mlp_in(s);
   UG_STEP_ROWS2(s);
   const float shift = ug_step_shift(s);
   if (s->M1 > 0 && s->mode == 2) {
@@ -188,11 +194,16 @@ extern "C" int ugrid_voxgo_step_forward(const ugrid_voxgo_step *s, ugrid_stream_
   rc = (s->k0_channels_last ? ugrid_grid_query_cl : ugrid_grid_query)(s->k0_grid, s->kP, s->C, s->kX, s->kY, s->kZ, w.pts2, s->k0_xyz_min,
                                                                      s->k0_xyz_max, s->k0_freq_num, M2, s->colour == 1 ? s->logits : w.k0, st);
   if (rc) return rc;
-  if (s->colour == 0) {
-    rc = ugrid_rgbnet_features(w.k0, s->C, s->viewdirs, R, s->viewfreq, s->pe, s->ray_id2, M2, w.ray_rows, w.feat, st);
+  if (s->colour != 1) {
+    rc = (s->colour == 2 ? ugrid_rgbnet_features_residual : ugrid_rgbnet_features)(w.k0, s->C, s->viewdirs, R, s->viewfreq, s->pe, s->ray_id2,
+                                                                                  M2, w.ray_rows, w.feat, st);
     if (rc) return rc;
     rc = ugrid_rgbnet_train_forward(w.feat, M2, K, s->w0, s->b0, s->w1, s->b1, s->w2, s->b2, s->width, w.h1, w.h2, s->logits, st);
     if (rc) return rc;
+    if (s->colour == 2) {                               // + the diffuse channels (dvgo.py:396)
+      rc = ugrid_residual_logits(s->logits, w.k0, s->C, M2, st);
+      if (rc) return rc;
+    }
   }
   return ugrid_render_loss(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9, s->seg,
                            s->rgb_marched, s->ray_tot, s->partial, s->out2, st);
@@ -206,16 +217,21 @@ extern "C" int ugrid_voxgo_step_backward_k0(const ugrid_voxgo_step *s, ugrid_str
   const ug_step_ws w = ug_step_layout(s);
   const ug_step_ws_bwd b = ug_step_layout_bwd(s);
   const int64_t R = s->n_rays, M2 = s->M2;
-  const int K = s->C + 3 + 6 * s->pe;
+  const int K = ug_step_mlp_in(s);
   UG_STEP_ROWS2(s);
   rc = ugrid_render_loss_backward(s->logits, s->weights2, ug_step_s(s), s->t2, s->alphainv_last, s->bg, s->target, s->ray_id2, M2, R, s->coef9,
                                   s->seg, s->rgb_marched, s->ray_tot, s->grad_loss, b.g_logits, b.g_w, b.g_ainv, b.g_dens, st);
   if (rc) return rc;
   const float *g_k0 = b.g_logits;                      // colour 1: the logits are the lookup's output
-  if (s->colour == 0) {
-    rc = ugrid_rgbnet_train_backward(b.g_logits, w.feat, w.h1, w.h2, M2, K, s->C, s->w0, s->w1, s->w2, s->width, b.g_k0, s->g_w0, s->g_b0,
-                                     s->g_w1, s->g_b1, s->g_w2, s->g_b2, b.rg, st);
+  if (s->colour != 1) {
+    const bool res = s->colour == 2;                   // the network's input gradient covers k0[:, 3:], g_logits is that of k0[:, :3]
+    rc = ugrid_rgbnet_train_backward(b.g_logits, w.feat, w.h1, w.h2, M2, K, res ? s->C - 3 : s->C, s->w0, s->w1, s->w2, s->width,
+                                     res ? b.g_feat : b.g_k0, s->g_w0, s->g_b0, s->g_w1, s->g_b1, s->g_w2, s->g_b2, b.rg, st);
     if (rc) return rc;
+    if (res) {
+      rc = ugrid_residual_k0_grad(b.g_logits, b.g_feat, s->C, M2, b.g_k0, st);
+      if (rc) return rc;
+    }
     g_k0 = b.g_k0;
   }
   if (s->k0_channels_last && s->touch)

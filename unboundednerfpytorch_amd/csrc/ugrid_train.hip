@@ -286,8 +286,8 @@ extern "C" int ugrid_render_loss_backward(const float *logits, const float *weig
 // (viewdirs.unsqueeze(-1) * viewfreq).flatten(-2): axis-major, frequency-minor.
 template <typename IDX>      // uint32_t when the element count fits (a 64-bit division is ~100 VALU instructions, the kernel's largest cost)
 __global__ void __launch_bounds__(256)
-k_rgbnet_features(const float *__restrict__ k0, int C, const float *__restrict__ viewdirs, const float *__restrict__ freq, int pe,
-                  const int64_t *__restrict__ ray_id, int64_t total, float *__restrict__ out, const int64_t *__restrict__ n_dev) {
+k_rgbnet_features(const float *__restrict__ k0, int C, int ks, int ko, const float *__restrict__ viewdirs, const float *__restrict__ freq,
+                  int pe, const int64_t *__restrict__ ray_id, int64_t total, float *__restrict__ out, const int64_t *__restrict__ n_dev) {
   const int K = C + 3 + 6 * pe;
   if (n_dev) {                                   // rows on the device (ug_devn): total = rows * K
     const int64_t td = *n_dev * K;
@@ -297,7 +297,7 @@ k_rgbnet_features(const float *__restrict__ k0, int C, const float *__restrict__
     const int64_t m = (int64_t)((IDX)idx / (IDX)K);
     const int j = (int)(idx - m * K);
     if (j < C) {
-      out[idx] = k0[m * C + j];
+      out[idx] = k0[m * ks + ko + j];
       continue;
     }
     const float *v = viewdirs + 3 * (ray_id ? ray_id[m] : m);
@@ -319,8 +319,8 @@ k_rgbnet_features(const float *__restrict__ k0, int C, const float *__restrict__
 // a ray's ~15 surviving samples share its 24 sines and cosines, which were most of the one-pass kernel's time
 template <typename IDX>
 __global__ void __launch_bounds__(256)
-k_rgbnet_rows(const float *__restrict__ k0, int C, const float *__restrict__ ray_rows, int E, const int64_t *__restrict__ ray_id,
-              int64_t total, float *__restrict__ out, const int64_t *__restrict__ n_dev) {
+k_rgbnet_rows(const float *__restrict__ k0, int C, int ks, int ko, const float *__restrict__ ray_rows, int E,
+              const int64_t *__restrict__ ray_id, int64_t total, float *__restrict__ out, const int64_t *__restrict__ n_dev) {
   const int K = C + E;
   if (n_dev) {
     const int64_t td = *n_dev * K;
@@ -329,12 +329,14 @@ k_rgbnet_rows(const float *__restrict__ k0, int C, const float *__restrict__ ray
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t m = (int64_t)((IDX)idx / (IDX)K);
     const int j = (int)(idx - m * K);
-    out[idx] = j < C ? k0[m * C + j] : ray_rows[ray_id[m] * E + (j - C)];
+    out[idx] = j < C ? k0[m * ks + ko + j] : ray_rows[ray_id[m] * E + (j - C)];
   }
 }
 
-extern "C" int ugrid_rgbnet_features(const float *k0, int32_t n_k0, const float *viewdirs, int64_t n_rays, const float *viewfreq, int32_t pe,
-                                     const int64_t *ray_id, int64_t m, float *ray_rows, float *out, ugrid_stream_t st) {
+// the n_k0 feature columns of row i are k0[i * ks + ko + (0 .. n_k0)]: ks = the row stride of k0, ko = its first column
+static int ug_rgbnet_features(const float *k0, int32_t n_k0, int32_t ks, int32_t ko, const float *viewdirs, int64_t n_rays,
+                              const float *viewfreq, int32_t pe, const int64_t *ray_id, int64_t m, float *ray_rows, float *out,
+                              ugrid_stream_t st) {
   if (n_k0 < 0 || pe < 0 || m < 0 || n_rays < 0) return (int)hipErrorInvalidValue;
   const int E = 3 + 6 * pe;
   const int64_t total = m * (n_k0 + E);
@@ -348,13 +350,80 @@ extern "C" int ugrid_rgbnet_features(const float *k0, int32_t n_k0, const float 
   if (ray_id && ray_rows && n_rays > 0 && m >= 2 * n_rays) {
     const int64_t per_ray = n_rays * E;
     const int64_t total_l = ug_launch_rows(m) * (n_k0 + E);
-    UG_FEAT(k_rgbnet_features, per_ray, per_ray, nullptr, 0, viewdirs, viewfreq, pe, nullptr, per_ray, ray_rows, (const int64_t *)nullptr)
-    UG_FEAT(k_rgbnet_rows, total_l, total, k0, n_k0, ray_rows, E, ray_id, total, out, ug_tl_devn.ptr)
+    UG_FEAT(k_rgbnet_features, per_ray, per_ray, nullptr, 0, 0, 0, viewdirs, viewfreq, pe, nullptr, per_ray, ray_rows, (const int64_t *)nullptr)
+    UG_FEAT(k_rgbnet_rows, total_l, total, k0, n_k0, ks, ko, ray_rows, E, ray_id, total, out, ug_tl_devn.ptr)
   } else {
     const int64_t total_l = ug_launch_rows(m) * (n_k0 + E);
-    UG_FEAT(k_rgbnet_features, total_l, total, k0, n_k0, viewdirs, viewfreq, pe, ray_id, total, out, ug_tl_devn.ptr)
+    UG_FEAT(k_rgbnet_features, total_l, total, k0, n_k0, ks, ko, viewdirs, viewfreq, pe, ray_id, total, out, ug_tl_devn.ptr)
   }
-#undef UG_FEAT
   UG_LAUNCH_CHECK();
   return 0;
 }
+
+extern "C" int ugrid_rgbnet_features(const float *k0, int32_t n_k0, const float *viewdirs, int64_t n_rays, const float *viewfreq, int32_t pe,
+                                     const int64_t *ray_id, int64_t m, float *ray_rows, float *out, ugrid_stream_t st) {
+  return ug_rgbnet_features(k0, n_k0, n_k0, 0, viewdirs, n_rays, viewfreq, pe, ray_id, m, ray_rows, out, st);
+}
+
+// ---- the residual-colour rgbnet of DirectVoxGO (rgbnet_direct = False, dvgo.py:384-398) ----------------------------------------
+// rgb = sigmoid(rgbnet([k0[:, 3:] | view embedding]) + k0[:, :3]): the network sees the feature channels behind the three diffuse
+// ones, which are added to its output.  Three elementwise leaves around the rgbnet's own launchers; each takes its row count like
+// the kernels above (ug_devn: the sync-free step).
+
+// rows [k0[:, 3:] | viewdir | sin | cos]: the kernels above reading k0 with row stride C from column 3 -- no contiguous copy
+extern "C" int ugrid_rgbnet_features_residual(const float *k0, int32_t C, const float *viewdirs, int64_t n_rays, const float *viewfreq,
+                                              int32_t pe, const int64_t *ray_id, int64_t m, float *ray_rows, float *out, ugrid_stream_t st) {
+  if (C < 4 || pe < 0 || m < 0 || n_rays < 0) return (int)hipErrorInvalidValue;
+  if (m == 0) return 0;
+  if (!k0) return (int)hipErrorInvalidValue;
+  return ug_rgbnet_features(k0, C - 3, C, 3, viewdirs, n_rays, viewfreq, pe, ray_id, m, ray_rows, out, st);
+}
+
+// logits[i, c] += k0[i, c], c < 3
+__global__ void __launch_bounds__(256)
+k_residual_logits(float *__restrict__ logits, const float *__restrict__ k0, int C, int64_t total, const int64_t *__restrict__ n_dev) {
+  if (n_dev) {                                   // rows on the device (ug_devn): total = rows * 3
+    const int64_t td = *n_dev * 3;
+    if (td < total) total = td;
+  }
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = idx / 3;
+    logits[idx] += k0[i * C + (idx - 3 * i)];
+  }
+}
+
+extern "C" int ugrid_residual_logits(float *logits, const float *k0, int32_t C, int64_t m, ugrid_stream_t st) {
+  if (C < 4 || m < 0) return (int)hipErrorInvalidValue;
+  if (m == 0) return 0;
+  if (!logits || !k0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_residual_logits, dim3(ug_blocks(ug_launch_rows(m) * 3, 256)), dim3(256), 0, ST(st), logits, k0, C, m * 3, ug_tl_devn.ptr);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+// g_k0[i] = [g_logits[i] | g_feat[i]]: the diffuse channels take the logits' gradient, the others the rgbnet's input gradient
+template <typename IDX>
+__global__ void __launch_bounds__(256)
+k_residual_k0_grad(const float *__restrict__ g_logits, const float *__restrict__ g_feat, int C, int64_t total, float *__restrict__ g_k0,
+                   const int64_t *__restrict__ n_dev) {
+  if (n_dev) {
+    const int64_t td = *n_dev * C;
+    if (td < total) total = td;
+  }
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)((IDX)idx / (IDX)C);
+    const int c = (int)(idx - i * C);
+    g_k0[idx] = c < 3 ? g_logits[3 * i + c] : g_feat[i * (C - 3) + (c - 3)];
+  }
+}
+
+extern "C" int ugrid_residual_k0_grad(const float *g_logits, const float *g_feat, int32_t C, int64_t m, float *g_k0, ugrid_stream_t st) {
+  if (C < 4 || m < 0) return (int)hipErrorInvalidValue;
+  if (m == 0) return 0;
+  if (!g_logits || !g_feat || !g_k0) return (int)hipErrorInvalidValue;
+  const int64_t total = m * C, total_l = ug_launch_rows(m) * C;
+  UG_FEAT(k_residual_k0_grad, total_l, total, g_logits, g_feat, C, total, g_k0, ug_tl_devn.ptr)
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+#undef UG_FEAT

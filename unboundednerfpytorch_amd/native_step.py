@@ -76,7 +76,9 @@ class VoxGOStep(torch.autograd.Function):
     then the samples' s, and the loss takes it as both s and t), xyz_min / xyz_max, k0_xyz_min / k0_xyz_max, mask (bool [mi,mj,mk];
     none for 'fourier'), target [R,3], bg [R,3] or None, coef (ops.loss_coefficients).
     pack['colour'] (optional) 'none': the coarse stage -- no rgbnet, the colour logits are the 3-channel k0 lookup itself (ugrid_voxgo_step.colour
-    = 1); the six weights are passed as None and get no gradient, viewdirs / viewfreq are not read.
+    = 1); the six weights are passed as None and get no gradient, viewdirs / viewfreq are not read.  'residual': DirectVoxGO's
+    residual-colour rgbnet (rgbnet_direct = False, colour = 2) -- logits = rgbnet([k0[:, 3:] | view embedding]) + k0[:, :3]; a k0 grid of
+    C >= 4 channels, w0 [W, C + 6 pe]; raw_logits are the full logits, diffuse channels included.
     pack['sync_free'] (optional: True or {'capacity': rows of the stage-2 arrays (default rays x slots: cannot overflow), 'hints': (M1, M2)
     expected counts}): the step makes no host read and synchronises nothing -- forward and backward only enqueue work, the whole step can
     run ahead of the host or be captured in a hipGraph (include/ugrid_hip.h ugrid_voxgo_step.sync_free).  The per-sample outputs then
@@ -91,13 +93,24 @@ class VoxGOStep(torch.autograd.Function):
     def forward(ctx, density_grid, k0_grid, w0, b0, w1, b1, w2, b2, pack):
         cfg, mode = pack['cfg'], pack['mode']
         # (dense copies where a caller hands in views: the op-by-op ops do the same)
-        net = pack.get('colour') != 'none'
+        colour = pack.get('colour') or 'rgbnet'
+        if colour not in ('rgbnet', 'none', 'residual'):
+            raise RuntimeError("VoxGOStep: colour must be 'rgbnet', 'none' or 'residual' (got %r)" % (colour,))
+        net, residual = colour != 'none', colour == 'residual'
         rays_o, rays_d, target = (pack[k].contiguous() for k in ('rays_o', 'rays_d', 'target'))
         viewdirs, viewfreq = (pack[k].contiguous() for k in ('viewdirs', 'viewfreq')) if net else (None, None)
         bg = pack['bg'].contiguous() if pack.get('bg') is not None else None
         if not net and any(x is not None for x in (w0, b0, w1, b1, w2, b2)):
             raise RuntimeError("VoxGOStep: colour 'none' has no rgbnet -- pass None for its six weights")
         ws_ = [x.contiguous() for x in (w0, b0, w1, b1, w2, b2)] if net else []
+        if residual:
+            # the diffuse channels come off the front of k0: the network's first layer is 3 columns narrower than the direct model's
+            C_, pe_ = (k0_grid.shape[1] if k0_grid.dim() == 5 else -1), viewfreq.numel()
+            if C_ < 4:
+                raise RuntimeError("VoxGOStep: colour 'residual' takes a k0 grid [P,C,X,Y,Z] of at least 4 channels, 3 diffuse + the "
+                                   "rgbnet's (got %d)" % C_)
+            if ws_[0].dim() != 2 or ws_[0].shape[1] != C_ + 6 * pe_:
+                raise RuntimeError("VoxGOStep: colour 'residual': w0 must be [W, C+6pe] = [W, %d] (got %s)" % (C_ + 6 * pe_, tuple(ws_[0].shape)))
         f32 = [("density grid", density_grid), ("rays_o", rays_o), ("rays_d", rays_d), ("target", target)] \
             + ([("viewdirs", viewdirs), ("viewfreq", viewfreq)] if net else []) + [("rgbnet", x) for x in ws_]
         if bg is not None:
@@ -146,7 +159,9 @@ class VoxGOStep(torch.autograd.Function):
         S = int(cfg['slots']) if mode == 'dvgo' else int(cfg['n_steps']) if mode == 'mpi' else t.numel()
         C = k0_grid.shape[1]
         W, pe = (ws_[0].shape[0], viewfreq.numel()) if net else (0, 0)
-        if net and (tuple(ws_[0].shape) != (W, C + 3 + 6 * pe) or tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W)):
+        if residual and (tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W)):
+            raise RuntimeError("VoxGOStep: colour 'residual': rgbnet weights must be [W, C+6pe], [W,W], [3,W]")
+        if net and not residual and (tuple(ws_[0].shape) != (W, C + 3 + 6 * pe) or tuple(ws_[2].shape) != (W, W) or tuple(ws_[4].shape) != (3, W)):
             raise RuntimeError("VoxGOStep: rgbnet weights must be [W, C+3+6pe], [W,W], [3,W]")
         if not net and C != 3:
             raise RuntimeError("VoxGOStep: colour 'none' takes a 3-channel k0 grid (got %d channels)" % C)
@@ -162,7 +177,7 @@ class VoxGOStep(torch.autograd.Function):
         s = _lib.VoxgoStep()
         s.mode = {'dvgo': 0, 'dcvgo': 1, 'fourier': 2, 'mpi': 3}[mode]
         s.k0_channels_last = int(k0_cl)
-        s.colour = 0 if net else 1
+        s.colour = 2 if residual else 0 if net else 1
         s.P, s.kP = density_grid.shape[0], k0_grid.shape[0]
         s.freq_num, s.k0_freq_num = (max(int(cfg['freq_num']), 0), max(int(cfg['k0_freq_num']), 0)) if mode == 'fourier' else (0, 0)
         s.X, s.Y, s.Z = density_grid.shape[2:]

@@ -39,6 +39,9 @@ class TrainModel(nn.Module):
     native_coarse = False       # True: the coarse stage (no rgbnet, 3-channel k0) of DirectVoxGO / DirectContractedVoxGO also takes
                                 # native_step.VoxGOStep (colour 'none'); the other models ignore it
     _native_coarse_ok = False   # (the models whose forward passes the colour mode on)
+    native_residual = False     # True: DirectVoxGO's residual-colour rgbnet (rgbnet_direct = False: rgbnet(k0[:, 3:], view) + k0[:, :3])
+                                # also takes native_step.VoxGOStep (colour 'residual'); the other models ignore it
+    _native_residual_ok = False
 
     # -- construction helpers ------------------------------------------------------------------------------
     def _make_grid(self, channels, world_size, fourier, channels_last):
@@ -133,7 +136,8 @@ class TrainModel(nn.Module):
         the model has the choice), gradients on, every one of those parameters trainable, and both grids looked up by the HIP kernels
         (no injected query function) with the levels they were built with.
         The coarse stage -- no rgbnet, the colour is the 3-channel k0 itself -- takes the native step only where `native_coarse` asks
-        for it: the two grids followed by six None (VoxGOStep colour 'none')."""
+        for it: the two grids followed by six None (VoxGOStep colour 'none').  The residual-colour rgbnet (rgbnet_direct = False) takes it
+        only where `native_residual` asks for it, under the conditions of the direct one plus a k0 of >= 4 channels (colour 'residual')."""
         if not (self.native_step and torch.is_grad_enabled()):
             return None
         if self.rgbnet is None:
@@ -141,7 +145,9 @@ class TrainModel(nn.Module):
                 return None
             nets = [None] * 6
         else:
-            if not (self.fused_rgbnet and getattr(self, 'rgbnet_direct', True)):
+            if not self.fused_rgbnet:
+                return None
+            if self._residual_colour() and not (self.native_residual and self._native_residual_ok and self.k0.grid.shape[1] >= 4):
                 return None
             lin = _ops.rgbnet_linears(self.rgbnet)
             if lin is None:
@@ -153,12 +159,16 @@ class TrainModel(nn.Module):
             return None
         return params
 
+    def _residual_colour(self):
+        """the rgbnet sees k0[:, 3:] and its output is added to k0[:, :3] (DirectVoxGO with rgbnet_direct = False)"""
+        return self.rgbnet is not None and not getattr(self, 'rgbnet_direct', True)
+
     def _native_forward(self, params, mode, cfg, t, rays_o, rays_d, viewdirs, fused_loss, bg, mask):
         """The training forward + loss as ONE autograd node issued from C (native_step.VoxGOStep): the same kernels, sizes and order
         as the op-by-op ops; the reference's return dict with loss / mse added, the per-sample arrays detached"""
         from .native_step import VoxGOStep
         pack = {'mode': mode, 'cfg': cfg, 't': t, 'rays_o': rays_o, 'rays_d': rays_d, 'viewdirs': viewdirs,
-                'viewfreq': self.viewfreq if self.rgbnet is not None else None, 'colour': 'none' if self.rgbnet is None else 'rgbnet',
+                'viewfreq': self.viewfreq if self.rgbnet is not None else None, 'colour': 'none' if self.rgbnet is None else 'residual' if self._residual_colour() else 'rgbnet',
                 'xyz_min': self.xyz_min, 'xyz_max': self.xyz_max, 'k0_xyz_min': self.k0.xyz_min, 'k0_xyz_max': self.k0.xyz_max,
                 'mask': mask, 'target': fused_loss['target'], 'bg': bg, 'coef': fused_loss['coef'], 'sync_free': self.native_sync_free}
         loss, mse = VoxGOStep.apply(*params, pack)

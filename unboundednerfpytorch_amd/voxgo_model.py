@@ -35,7 +35,8 @@ class _VoxGOBase(TrainModel):
     native_sync_free = False    # True / {'capacity': rows}: that node without its host read (capacity-sized per-sample arrays, counts
                                 # on the device; native_step.VoxGOStep pack['sync_free'])
                                 # (same kernels, same bits; default rgbnet, rgbnet_direct, train_iteration's fused_loss)
-                                # (TrainModel.native_coarse = True: the coarse stage -- rgbnet_dim = 0 -- of the two models below too)
+                                # (TrainModel.native_coarse = True: the coarse stage -- rgbnet_dim = 0 -- of the two models below too;
+                                # TrainModel.native_residual = True: DirectVoxGO with rgbnet_direct = False too)
 
     def _init_grids(self, density_type, k0_type, density_config, k0_config, k0_dim, channels_last):
         if density_type != 'DenseGrid' or k0_type != 'DenseGrid':
@@ -116,6 +117,7 @@ class _VoxGOBase(TrainModel):
 class DirectVoxGO(_VoxGOBase):
     """The bounded model (dvgo.py:26-425)."""
     _native_coarse_ok = True
+    _native_residual_ok = True
     fused_loss = True           # train_step.train_iteration: compositing + loss as ops.RenderLoss (no distortion / nearclip term)
 
     def sample_table(self, stepsize, device):
