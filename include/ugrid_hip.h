@@ -723,6 +723,41 @@ int ugrid_frame_metrics(const float *img, int64_t img_stride, const float *gt, i
                         int64_t W, int32_t filter_size, double filter_sigma, double k1, double k2,
                         double max_val, double *out, double *map, void *ws, ugrid_stream_t stream);
 
+/* ------------------------------------------------------------------ TensoRF (vector-matrix) grids (csrc/ugrid_tensorf.hip)
+ * The reference's TensoRFGrid (FourierGrid/grid.py:90-201).  Factors of one grid of world size X x Y x Z with R components
+ * (Rxy for the xy pair): xy_plane [1,Rxy,X,Y] pairs with z_vec [1,Rxy,Z,1], xz_plane [1,R,X,Z] with y_vec [1,R,Y,1],
+ * yz_plane [1,R,Y,Z] with x_vec [1,R,X,1]; f_vec [Rxy+R+R, C] (rows in the order xy*z | xz*y | yz*x; unused, may be NULL, for
+ * C == 1).  comp_last = 0: those canonical layouts; 1: component-last storage of the same logical tensors (torch.channels_last:
+ * planes [A][B][R], vectors [N][R]), all six factors and their gradients alike.
+ * Coordinates as grid_sample(align_corners = True, zeros padding): u = (x - xyz_min) / (xyz_max - xyz_min) * 2 - 1, index
+ * (u + 1) / 2 * (n - 1), a vertex outside [0, n-1] contributes nothing.
+ * Limits (hipErrorInvalidValue, before anything touches the device): 1 <= C <= 16 and (Rxy + 2 R) * C <= 3072.
+ *
+ * _query: out [n] (C == 1) or [n, C], fully written.
+ * _query_backward: grad_out [n] or [n, C]; the seven gradients (g_f_vec only for C > 1) are ZEROED by the call and then
+ *   accumulated (also for n == 0); xyz gets no gradient.  Float atomics: sums agree to rounding, not bit for bit.
+ * _tv_add_grad: adds the gradient of the reference's total_variation_add_grad (grid.py:142-154: smooth-L1, beta 1, of every
+ *   adjacent pair, weight wx / wy / wz by the pair's axis, / 6) to the six gradients in place; gather form, deterministic.
+ * _bake: the dense grid of get_dense_grid (grid.py:156-169), out [1,C,X,Y,Z] (out_channels_last = 0) or the same logical tensor
+ *   stored [X][Y][Z][C] (1), fully written, no intermediate. */
+int ugrid_tensorf_query(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                        const float *y_vec, const float *z_vec, const float *f_vec, int X, int Y, int Z, int R, int Rxy,
+                        int C, int comp_last, const float *xyz, const float *xyz_min, const float *xyz_max, int64_t n,
+                        float *out, ugrid_stream_t stream);
+int ugrid_tensorf_query_backward(const float *grad_out, const float *xy_plane, const float *xz_plane, const float *yz_plane,
+                                 const float *x_vec, const float *y_vec, const float *z_vec, const float *f_vec, int X,
+                                 int Y, int Z, int R, int Rxy, int C, int comp_last, const float *xyz,
+                                 const float *xyz_min, const float *xyz_max, int64_t n, float *g_xy_plane,
+                                 float *g_xz_plane, float *g_yz_plane, float *g_x_vec, float *g_y_vec, float *g_z_vec,
+                                 float *g_f_vec, ugrid_stream_t stream);
+int ugrid_tensorf_tv_add_grad(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                              const float *y_vec, const float *z_vec, float *g_xy_plane, float *g_xz_plane,
+                              float *g_yz_plane, float *g_x_vec, float *g_y_vec, float *g_z_vec, int X, int Y, int Z,
+                              int R, int Rxy, int comp_last, float wx, float wy, float wz, ugrid_stream_t stream);
+int ugrid_tensorf_bake(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                       const float *y_vec, const float *z_vec, const float *f_vec, int X, int Y, int Z, int R, int Rxy,
+                       int C, int comp_last, int out_channels_last, float *out, ugrid_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,10 @@ _SIGNATURES = {
     "ugrid_render_stats": (_I, [_P, _L, _c.c_int32, _P, _P]),
     "ugrid_frame_metrics_ws_bytes": (_L, [_L, _L]),
     "ugrid_frame_metrics": (_I, [_P, _L, _P, _L, _L, _L, _c.c_int32, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _P, _P, _P, _P]),
+    "ugrid_tensorf_query": (_I, [_P] * 7 + [_I] * 7 + [_P, _P, _P, _L, _P, _P]),
+    "ugrid_tensorf_query_backward": (_I, [_P] * 8 + [_I] * 7 + [_P, _P, _P, _L] + [_P] * 8),
+    "ugrid_tensorf_tv_add_grad": (_I, [_P] * 12 + [_I] * 6 + [_F, _F, _F, _P]),
+    "ugrid_tensorf_bake": (_I, [_P] * 7 + [_I] * 8 + [_P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -334,6 +338,22 @@ def require_cuda_grid(*named):
     if any(cl) and not all(cl):
         raise RuntimeError("grid tensors %s mix the canonical and the channel-last layout" % ", ".join(n for n, _ in named))
     return all(cl) and len(cl) > 0
+
+
+def is_comp_last(t):
+    """A 4-D [1,R,A,B] tensor stored [A][B][R] (torch.channels_last) -- the storage of grid.TensoRFGrid's factors (R > 1; with
+    R == 1 the two layouts coincide and the tensor counts as canonical)."""
+    return t.dim() == 4 and t.shape[1] > 1 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def require_cuda_comp_last(*named):
+    """CHECK_INPUT for elementwise ops over 4-D tensors stored component-last: device-resident, dense in that layout, one set of
+    strides for all of them (the op walks the storage)."""
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError("%s must be a CUDA tensor" % name)
+        if not is_comp_last(t) or t.stride() != named[0][1].stride():
+            raise RuntimeError("%s must be contiguous" % name)
 
 
 def wait_pending(param):

@@ -12,8 +12,13 @@ def _run(param, grad, exp_avg, exp_avg_sq, perlr, step, beta1, beta2, lr, eps, m
     if perlr is not None:
         named.append(("perlr", perlr))
     # elementwise over the storage: any dense layout works as long as all operands share it (canonical, or the
-    # channel-last training layout of grid.FourierGrid)
-    _lib.require_cuda_grid(*named) if param.dim() == 5 else _lib.require_cuda(*named)
+    # channel-last training layout of grid.FourierGrid, or the component-last one of grid.TensoRFGrid's 4-D factors)
+    if param.dim() == 5:
+        _lib.require_cuda_grid(*named)
+    elif _lib.is_comp_last(param):
+        _lib.require_cuda_comp_last(*named)
+    else:
+        _lib.require_cuda(*named)
     dt = _lib.real_dtype(*named)
     if dt == torch.float64 and mode == 3:
         raise RuntimeError("masked_adam_upd_rezero: float32 only (no reference counterpart)")

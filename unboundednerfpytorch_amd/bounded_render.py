@@ -11,6 +11,52 @@ import torch
 import torch.nn.functional as F
 
 
+def bake_tensorf_checkpoint(ckpt, device, mem_get_info=None):
+    """A checkpoint of a model with TensoRF grids (grid.TensoRFGrid: `density.xy_plane` ... `k0.f_vec`) as the checkpoint of the
+    same model with dense grids: every TensoRF grid is baked ON `device` by one kernel (grid.tensorf_bake -- exact: trilinear weights
+    are separable, so trilinear interpolation of the baked grid equals the factorised interpolation term by term) into the canonical
+    [1,C,X,Y,Z] layout the brick packer reads; a dense grid passes through.  The renderers' existing state functions, fused march and
+    shade kernels then apply unchanged.
+    Before baking, the baked byte count is compared with the device's free memory (mem_get_info(device) -> (free, total), default
+    torch.cuda.mem_get_info): RuntimeError naming both numbers if it does not fit."""
+    from . import grid as _grid
+    kw, sd = dict(ckpt['model_kwargs']), dict(ckpt['model_state_dict'])
+    dev = torch.device(device)
+    todo = [g for g in ('density', 'k0') if kw.get(g + '_type', 'DenseGrid') == 'TensoRFGrid']
+    if not todo:
+        raise ValueError("no TensoRFGrid in this checkpoint: use from_reference_checkpoint")
+    shapes = {}
+    for g in todo:
+        X, Y = sd[g + '.xy_plane'].shape[2:]
+        Z = sd[g + '.xz_plane'].shape[3]
+        C = sd[g + '.f_vec'].shape[1] if g + '.f_vec' in sd else 1
+        shapes[g] = (int(C), int(X), int(Y), int(Z))
+    need = sum(4 * c * x * y * z for c, x, y, z in shapes.values())
+    free = int((mem_get_info or torch.cuda.mem_get_info)(dev)[0])
+    if need > free:
+        raise RuntimeError("baking the TensoRF grids %s of this checkpoint needs %d bytes on %s, %d bytes are free" % (
+            ", ".join("%s %s" % (g, list(shapes[g])) for g in todo), need, dev, free))
+    for g in todo:
+        factors = tuple(sd.pop(g + '.' + n).to(dev, torch.float32).contiguous() for n in _grid.TENSORF_FACTORS)
+        f_vec = sd.pop(g + '.f_vec').to(dev, torch.float32).contiguous() if g + '.f_vec' in sd else None
+        sd[g + '.grid'] = _grid.tensorf_bake(factors, f_vec)
+        kw[g + '_type'], kw[g + '_config'] = 'DenseGrid', {}
+    return {'model_kwargs': kw, 'model_state_dict': sd}
+
+
+def stored_buffers_win(state, ckpt, keys):
+    """`state` with the model's stored buffers in place of the values re-derived from `model_kwargs`.  The trainer changes them after
+    construction, and the reference reloads them with the state dict (utils.load_model): `act_shift` is lowered by decay_after_scale at
+    every pg_scale step (run_train.py:201), and DirectContractedVoxGO.get_kwargs saves the CONTRACTED bounds as xyz_min / xyz_max
+    (dcvgo.py:139-141), from which scene_center / scene_radius cannot be re-derived.  A state built without them renders another
+    scene than the one trained (colours off by up to 0.28 on the checkpoints of tests/test_gpu_tensorf_model.py)."""
+    sd = ckpt['model_state_dict']
+    for k in keys:
+        if k in sd:
+            state[k] = sd[k].detach().clone().float()
+    return state
+
+
 class BoundedRenderer:
     output_keys = ('rgb_marched', 'depth', 'alphainv_last')     # per-ray outputs the render program consumes (run_render.py:46)
     ndc = False               # render_view: forward-facing NDC rays

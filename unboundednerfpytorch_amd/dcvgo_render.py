@@ -62,6 +62,14 @@ def dcvgo_state_from_reference_checkpoint(ckpt):
     return st
 
 
+def dcvgo_state_from_tensorf_checkpoint(ckpt, device, mem_get_info=None):
+    """`state` from a DirectContractedVoxGO checkpoint whose density and / or k0 is a TensoRFGrid: the TensoRF grids baked on `device`
+    (bounded_render.bake_tensorf_checkpoint: exact, memory-checked), then dcvgo_state_from_reference_checkpoint"""
+    from .bounded_render import bake_tensorf_checkpoint, stored_buffers_win
+    return stored_buffers_win(dcvgo_state_from_reference_checkpoint(bake_tensorf_checkpoint(ckpt, device, mem_get_info)), ckpt,
+                              ('act_shift', 'scene_center', 'scene_radius'))
+
+
 class DirectContractedVoxGORenderer(BoundedRenderer):
     """render_rays: the whole chain of dcvgo.py:228-384 in two launches, no [N,S,3] point tensor, no boolean compactions;
     render_kwargs as forward(): stepsize, bg, render_depth, plus FourierGridRenderer's ray_order."""
@@ -75,6 +83,11 @@ class DirectContractedVoxGORenderer(BoundedRenderer):
     def from_reference_checkpoint(cls, ckpt, device):
         """ckpt: the dict the reference saves for a DirectContractedVoxGO model (torch.load('fine_last.tar', weights_only=False))"""
         return cls(dcvgo_state_from_reference_checkpoint(ckpt), device)
+
+    @classmethod
+    def from_tensorf_checkpoint(cls, ckpt, device, mem_get_info=None):
+        """ckpt: a DirectContractedVoxGO checkpoint with TensoRF grids; they are baked once on `device`, the fused kernels render the result"""
+        return cls(dcvgo_state_from_tensorf_checkpoint(ckpt, device, mem_get_info), device)
 
     # -- fused inference path: BoundedRenderer.fused_supported as it stands (the march is ugrid_render_march_dcvgo, the rgbnet the
     # 3 x 128 one on [k0 (12), view embedding]) ------------------------------------------------------------------

@@ -54,6 +54,13 @@ def dvgo_state_from_reference_checkpoint(ckpt):
     return st
 
 
+def dvgo_state_from_tensorf_checkpoint(ckpt, device, mem_get_info=None):
+    """`state` from a DirectVoxGO checkpoint whose density and / or k0 is a TensoRFGrid (configs/nerf/ship.tensorf.py): the TensoRF
+    grids baked on `device` (bounded_render.bake_tensorf_checkpoint: exact, memory-checked), then dvgo_state_from_reference_checkpoint"""
+    from .bounded_render import bake_tensorf_checkpoint, stored_buffers_win
+    return stored_buffers_win(dvgo_state_from_reference_checkpoint(bake_tensorf_checkpoint(ckpt, device, mem_get_info)), ckpt, ('act_shift',))
+
+
 class DirectVoxGORenderer(BoundedRenderer):
     """state: xyz_min/xyz_max [3], density_grid [1,1,X,Y,Z], k0_grid [1,C,X,Y,Z], rgbnet_weights/biases (lists),
     mask [mx,my,mz] bool, xyz2ijk_scale/shift [3], act_shift, voxel_size, voxel_size_ratio (0-d tensors or floats),
@@ -68,6 +75,11 @@ class DirectVoxGORenderer(BoundedRenderer):
     def from_reference_checkpoint(cls, ckpt, device):
         """ckpt: the dict the reference saves for a DirectVoxGO model (torch.load('fine_last.tar', weights_only=False))"""
         return cls(dvgo_state_from_reference_checkpoint(ckpt), device)
+
+    @classmethod
+    def from_tensorf_checkpoint(cls, ckpt, device, mem_get_info=None):
+        """ckpt: a DirectVoxGO checkpoint with TensoRF grids; they are baked once on `device`, the fused kernels render the result"""
+        return cls(dvgo_state_from_tensorf_checkpoint(ckpt, device, mem_get_info), device)
 
     # -- fused inference path ----------------------------------------------------------------------------------
     @property

@@ -332,9 +332,240 @@ def _sample_stages(ctx, grid, R, S, t, xyz_min, xyz_max, consts, freq_num, march
 
 
 def create_grid(type, **kwargs):
+    """grid.py:30-36 of the reference: 'DenseGrid' (here FourierGrid without Fourier levels) or 'TensoRFGrid'"""
     if type == 'DenseGrid':
+        kwargs.setdefault('use_nerf_pos', False)
+        kwargs.setdefault('fourier_freq_num', 0)
         return FourierGrid(**kwargs)
+    if type == 'TensoRFGrid':
+        return TensoRFGrid(**kwargs)
     raise NotImplementedError
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# TensoRF (vector-matrix) grids: grid.py:90-201 of the reference on csrc/ugrid_tensorf.hip
+# ---------------------------------------------------------------------------------------------------------------------------
+TENSORF_FACTORS = ('xy_plane', 'xz_plane', 'yz_plane', 'x_vec', 'y_vec', 'z_vec')
+
+
+def _tensorf_args(factors, f_vec, world_size=None):
+    """checks + (pointers of the six factors and f_vec), (X, Y, Z, R, Rxy, C), comp_last of one grid's tensors"""
+    xy, xz, yz, xv, yv, zv = factors
+    named = list(zip(TENSORF_FACTORS, factors)) + ([("f_vec", f_vec)] if f_vec is not None else [])
+    _lib.require_f32(*named)
+    for name, t in named:
+        if not t.is_cuda or t.device != xy.device:
+            raise RuntimeError("%s must be a CUDA tensor on the device of xy_plane" % name)
+    if any(t.dim() != 4 or t.shape[0] != 1 for t in factors):
+        raise RuntimeError("TensoRF factors are [1,R,A,B] planes and [1,R,N,1] vectors")
+    Rxy, X, Y = xy.shape[1:]
+    R, Z = xz.shape[1], xz.shape[3]
+    want = {'xy_plane': (1, Rxy, X, Y), 'xz_plane': (1, R, X, Z), 'yz_plane': (1, R, Y, Z), 'x_vec': (1, R, X, 1), 'y_vec': (1, R, Y, 1),
+            'z_vec': (1, Rxy, Z, 1)}
+    for name, t in zip(TENSORF_FACTORS, factors):
+        if tuple(t.shape) != want[name]:
+            raise RuntimeError("%s is %s, expected %s" % (name, tuple(t.shape), want[name]))
+    comp_last = any(_lib.is_comp_last(t) for t in factors)
+    for name, t in zip(TENSORF_FACTORS, factors):
+        if not (t.is_contiguous(memory_format=torch.channels_last) if comp_last else t.is_contiguous()):
+            raise RuntimeError("%s must be contiguous (the six factors share one layout, canonical or component-last)" % name)
+    C = 1
+    if f_vec is not None:
+        if f_vec.dim() != 2 or f_vec.shape[0] != R + R + Rxy or not f_vec.is_contiguous():
+            raise RuntimeError("f_vec must be a contiguous [R+R+Rxy, C]")
+        C = f_vec.shape[1]
+    if not 1 <= C <= 16 or (2 * R + Rxy) * C > 3072:
+        raise RuntimeError("TensoRF kernels: 1 <= channels <= 16 and (2 n_comp + n_comp_xy) * channels <= 3072 (got C=%d, R=%d, Rxy=%d)" % (C, R, Rxy))
+    return [_lib.ptr(t) for t in factors] + [_lib.ptr(f_vec)], (X, Y, Z, R, Rxy, C), int(comp_last)
+
+
+def _tensorf_points(xyz, xyz_min, xyz_max, dev):
+    pts = xyz.reshape(-1, 3).contiguous()
+    _lib.require_cuda(("xyz", pts), ("xyz_min", xyz_min), ("xyz_max", xyz_max))
+    _lib.require_f32(("xyz", pts), ("xyz_min", xyz_min), ("xyz_max", xyz_max))
+    if pts.device != dev or xyz_min.device != dev or xyz_max.device != dev:
+        raise RuntimeError("the factors, xyz, xyz_min and xyz_max must be on the same device")
+    return pts
+
+
+@torch.no_grad()
+def tensorf_query(factors, f_vec, xyz, xyz_min, xyz_max):
+    """factors (xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec), f_vec [R+R+Rxy, C] or None (C == 1); xyz [..., 3] world
+    coordinates -> [...] (C == 1) or [..., C]: TensoRFGrid.forward (grid.py:111-129), no autograd"""
+    ptrs, dims, cl = _tensorf_args(factors, f_vec)
+    C = dims[5]
+    dev = factors[0].device
+    pts = _tensorf_points(xyz, xyz_min, xyz_max, dev)
+    out = torch.empty((pts.shape[0], C) if f_vec is not None else (pts.shape[0],), dtype=torch.float32, device=dev)
+    with _lib.guard(dev):
+        _lib.check(_L.ugrid_tensorf_query(*ptrs, *dims, cl, _lib.ptr(pts), _lib.ptr(xyz_min), _lib.ptr(xyz_max), pts.shape[0], _lib.ptr(out),
+                                          _lib.stream_of(pts)), "tensorf_query")
+    return out.reshape(*xyz.shape[:-1], C) if f_vec is not None else out.reshape(xyz.shape[:-1])
+
+
+@torch.no_grad()
+def tensorf_query_backward(grad_out, factors, f_vec, pts, xyz_min, xyz_max, grads=None):
+    """gradients of tensorf_query's output w.r.t. the six factors and f_vec (None for C == 1), each in its tensor's own layout.
+    grads: seven caller-allocated tensors to write into (tests); default: new ones"""
+    ptrs, dims, cl = _tensorf_args(factors, f_vec)
+    dev = factors[0].device
+    pts = _tensorf_points(pts, xyz_min, xyz_max, dev)
+    if grad_out.numel() != pts.shape[0] * dims[5]:
+        raise RuntimeError("grad_out must be [n] or [n, C] on the factors' device")
+    g = grad_out.reshape(pts.shape[0], dims[5]).to(torch.float32).contiguous()
+    if g.device != dev:
+        raise RuntimeError("grad_out must be [n] or [n, C] on the factors' device")
+    if grads is None:
+        grads = [torch.empty_like(t, memory_format=torch.preserve_format) for t in factors] + [torch.empty_like(f_vec) if f_vec is not None else None]
+    with _lib.guard(dev):
+        _lib.check(_L.ugrid_tensorf_query_backward(_lib.ptr(g), *ptrs, *dims, cl, _lib.ptr(pts), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
+                                                   pts.shape[0], *[_lib.ptr(t) for t in grads], _lib.stream_of(pts)), "tensorf_query_backward")
+    return grads
+
+
+@torch.no_grad()
+def tensorf_tv_add_grad(factors, grads, wx, wy, wz):
+    """adds the gradient of TensoRFGrid.total_variation_add_grad's loss (grid.py:142-154) to the six `grads` in place"""
+    ptrs, dims, cl = _tensorf_args(factors, None)
+    for (name, t), g in zip(zip(TENSORF_FACTORS, factors), grads):
+        if g.dtype != torch.float32 or g.device != t.device or g.shape != t.shape or g.stride() != t.stride():
+            raise RuntimeError("the gradient of %s must have its tensor's device, shape and layout" % name)
+    with _lib.guard(factors[0].device):
+        _lib.check(_L.ugrid_tensorf_tv_add_grad(*ptrs[:6], *[_lib.ptr(g) for g in grads], *dims[:5], cl, float(wx), float(wy), float(wz),
+                                                _lib.stream_of(factors[0])), "tensorf_tv_add_grad")
+
+
+@torch.no_grad()
+def tensorf_bake(factors, f_vec, channels_last=False, out=None):
+    """the dense [1,C,X,Y,Z] grid of TensoRFGrid.get_dense_grid (grid.py:156-169) in one kernel, no intermediate; channels_last:
+    stored [X][Y][Z][C] (torch.channels_last_3d of the same logical tensor, FourierGrid's training layout); out: a tensor of an
+    earlier call with the same arguments, written again instead of a new one"""
+    ptrs, dims, cl = _tensorf_args(factors, f_vec)
+    X, Y, Z, _, _, C = dims
+    if out is None:
+        out = _lib.empty_like_grid((1, C, X, Y, Z), bool(channels_last) and C > 1, factors[0].device)
+    elif tuple(out.shape) != (1, C, X, Y, Z) or out.dtype != torch.float32 or out.device != factors[0].device \
+            or _lib.is_channels_last(out) != (bool(channels_last) and C > 1) or not (out.is_contiguous() or _lib.is_channels_last(out)):
+        raise RuntimeError("out must be the float32 [1,C,X,Y,Z] tensor of this bake, in the layout asked for")
+    with _lib.guard(out.device):
+        _lib.check(_L.ugrid_tensorf_bake(*ptrs, *dims, cl, int(bool(channels_last) and C > 1), _lib.ptr(out), _lib.stream_of(out)), "tensorf_bake")
+    return out
+
+
+def tensorf_compose(factors, f_vec, xyz, xyz_min, xyz_max):
+    """The same lookup as a torch composition (six grid_sample calls, a concatenation and a product with f_vec), differentiable by
+    autograd on any device: the stand-in of the tests' CPU oracle (TensoRFGrid.query_fn) and the baseline of tools/bench_tensorf.py"""
+    xy, xz, yz, xv, yv, zv = factors
+    u = ((xyz.reshape(1, 1, -1, 3) - xyz_min) / (xyz_max - xyz_min)) * 2 - 1
+    u = torch.cat([u, torch.zeros_like(u[..., :1])], -1)
+
+    def tap(t, cols):
+        return F.grid_sample(t, u[..., cols], mode='bilinear', align_corners=True).flatten(0, 2).T
+    feats = [tap(xy, [1, 0]) * tap(zv, [3, 2]), tap(xz, [2, 0]) * tap(yv, [3, 1]), tap(yz, [2, 1]) * tap(xv, [3, 0])]
+    if f_vec is None:
+        return (feats[0].sum(-1) + feats[1].sum(-1) + feats[2].sum(-1)).reshape(xyz.shape[:-1])
+    return torch.mm(torch.cat(feats, -1), f_vec).reshape(*xyz.shape[:-1], f_vec.shape[1])
+
+
+class TensoRFQuery(torch.autograd.Function):
+    """tensorf_query as an autograd op: HIP forward, HIP backward into the six factors and f_vec (the interpolants are recomputed; only
+    the points are kept).  forward(xyz, xyz_min, xyz_max, xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, f_vec or None).
+    xyz gets NO gradient (None): like every lookup of this package -- rays carry none in the reference's training."""
+
+    @staticmethod
+    def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
+        factors, f_vec = tensors[:6], tensors[6]
+        out = tensorf_query(factors, f_vec, xyz, xyz_min, xyz_max)
+        ctx.save_for_backward(xyz.reshape(-1, 3).contiguous(), xyz_min, xyz_max, *[t for t in tensors if t is not None])
+        ctx.has_f = f_vec is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pts, xyz_min, xyz_max, *tensors = ctx.saved_tensors
+        grads = tensorf_query_backward(grad_out, tensors[:6], tensors[6] if ctx.has_f else None, pts, xyz_min, xyz_max)
+        return (None, None, None) + tuple(grads)
+
+
+class TensoRFGrid(torch.nn.Module):
+    """Vector-matrix decomposed grid; mirrors the reference's TensoRFGrid (grid.py:90-201): same constructor arguments, parameter
+    names and logical shapes (state_dict compatible), initialisation and methods, with the lookup, its backward, the total-variation
+    gradient and the dense bake on the HIP kernels.  `component_last = True` STORES the factors component-last (torch.channels_last
+    of the same logical [1,R,A,B] tensors: a texel's R components are one run; state dicts and checkpoints are unchanged).  The
+    default is the canonical layout: at configs/nerf/ship.tensorf.py's final shape the k0 query measured 0.16 ms canonical against
+    0.52 ms component-last, the density query 0.48 against 0.43 (profiles/tensorf/query.json)."""
+
+    component_last = False
+    # test hooks, as FourierGrid's: query_fn(factors, f_vec, xyz, xyz_min, xyz_max) (differentiable; e.g. tensorf_compose) and
+    # tv_module.tensorf_tv_add_grad(factors, grads, wx, wy, wz); None = the HIP kernels
+    query_fn = None
+    tv_module = None
+
+    def __init__(self, channels, world_size, xyz_min, xyz_max, config, component_last=None):
+        super().__init__()
+        self.channels = channels
+        self.world_size = world_size
+        self.config = config
+        if component_last is not None:
+            self.component_last = bool(component_last)
+        self.register_buffer('xyz_min', torch.Tensor(xyz_min))
+        self.register_buffer('xyz_max', torch.Tensor(xyz_max))
+        X, Y, Z = [int(v) for v in world_size]
+        R = config['n_comp']
+        Rxy = config.get('n_comp_xy', R)
+        # (the reference's draws, in its order: the same generator state gives the same factors)
+        self.xy_plane = torch.nn.Parameter(self._as_stored(torch.randn([1, Rxy, X, Y]) * 0.1))
+        self.xz_plane = torch.nn.Parameter(self._as_stored(torch.randn([1, R, X, Z]) * 0.1))
+        self.yz_plane = torch.nn.Parameter(self._as_stored(torch.randn([1, R, Y, Z]) * 0.1))
+        self.x_vec = torch.nn.Parameter(self._as_stored(torch.randn([1, R, X, 1]) * 0.1))
+        self.y_vec = torch.nn.Parameter(self._as_stored(torch.randn([1, R, Y, 1]) * 0.1))
+        self.z_vec = torch.nn.Parameter(self._as_stored(torch.randn([1, Rxy, Z, 1]) * 0.1))
+        if self.channels > 1:
+            self.f_vec = torch.nn.Parameter(torch.ones([R + R + Rxy, channels]))
+            torch.nn.init.kaiming_uniform_(self.f_vec, a=5 ** 0.5)
+
+    def _as_stored(self, t):
+        return t.contiguous(memory_format=torch.channels_last) if self.component_last else t.contiguous()
+
+    def factors(self):
+        return tuple(getattr(self, n) for n in TENSORF_FACTORS)
+
+    def _f_vec(self):
+        return self.f_vec if self.channels > 1 else None
+
+    def forward(self, xyz):
+        """xyz [..., 3] world coordinates -> [..., C] ([...] when C == 1)"""
+        if self.query_fn is not None:
+            return self.query_fn(self.factors(), self._f_vec(), xyz, self.xyz_min, self.xyz_max)
+        return TensoRFQuery.apply(xyz, self.xyz_min, self.xyz_max, *self.factors(), self._f_vec())
+
+    def scale_volume_grid(self, new_world_size):
+        """six bilinear resamplings, as the reference (grid.py:131-140); once per pg_scale step"""
+        if self.channels == 0:
+            return
+        X, Y, Z = [int(v) for v in new_world_size]
+        for name, size in (('xy_plane', [X, Y]), ('xz_plane', [X, Z]), ('yz_plane', [Y, Z]), ('x_vec', [X, 1]), ('y_vec', [Y, 1]), ('z_vec', [Z, 1])):
+            old = getattr(self, name).data.contiguous()
+            setattr(self, name, torch.nn.Parameter(self._as_stored(F.interpolate(old, size=size, mode='bilinear', align_corners=True))))
+
+    def total_variation_add_grad(self, wx, wy, wz, dense_mode):
+        """Add the total-variation gradient in place (grid.py:142-154); like the reference, dense_mode is ignored"""
+        ps = self.factors()
+        for p in ps:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.preserve_format)
+        fn = self.tv_module.tensorf_tv_add_grad if self.tv_module is not None else tensorf_tv_add_grad
+        fn(tuple(p.data for p in ps), tuple(p.grad for p in ps), float(wx), float(wy), float(wz))
+
+    def get_dense_grid(self, channels_last=False):
+        """the dense [1,C,X,Y,Z] grid (grid.py:156-169), baked by one kernel"""
+        f = self._f_vec()
+        return tensorf_bake(tuple(p.data for p in self.factors()), None if f is None else f.data, channels_last)
+
+    def extra_repr(self):
+        ws = self.world_size.tolist() if torch.is_tensor(self.world_size) else list(self.world_size)
+        return f'channels={self.channels}, world_size={ws}, n_comp={self.config["n_comp"]}'
 
 
 class FourierGrid(torch.nn.Module):

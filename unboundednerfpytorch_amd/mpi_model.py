@@ -50,6 +50,8 @@ class DirectMPIGO(_VoxGOBase):
         self._set_grid_resolution(num_voxels, mpi_depth)
         self.rgbnet_kwargs = {'rgbnet_dim': rgbnet_dim, 'rgbnet_depth': rgbnet_depth, 'rgbnet_width': rgbnet_width,
                               'viewbase_pe': viewbase_pe}
+        if density_type != 'DenseGrid' or k0_type != 'DenseGrid':
+            raise NotImplementedError("only DenseGrid (no config trains a TensoRF DirectMPIGO, and its per-axis TV differs)")
         # C = 9 (llff) is no multiple of 4: _make_grid keeps such a k0 in the canonical layout
         self._init_grids(density_type, k0_type, density_config, k0_config, 3 if rgbnet_dim <= 0 else rgbnet_dim,
                          backend is None and kwargs.get('channels_last_grids', True))

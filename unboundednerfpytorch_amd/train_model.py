@@ -105,8 +105,20 @@ class TrainModel(nn.Module):
         FourierGrid_model.py:392-418)"""
         from .train_rays import voxel_count_views
         return voxel_count_views(self._be.grid_query or _grid.GridQuery.apply, self.xyz_min, self.xyz_max, self.voxel_size_density,
-                                 self.world_size_density, self.density.get_dense_grid().shape, rays_o_tr, rays_d_tr, imsz, near,
+                                 self.world_size_density, self._density_grid_shape(), rays_o_tr, rays_d_tr, imsz, near,
                                  stepsize, downrate, irregular_shape)
+
+    def _has_tensorf(self, *grids):
+        """is one of `grids` (default: density and k0) a TensoRF grid?  Such a model takes the composed forward: there is no fused
+        sampling march and no native step over factorised grids"""
+        grids = grids or (getattr(self, 'density', None), getattr(self, 'k0', None))
+        return any(isinstance(g, _grid.TensoRFGrid) for g in grids)
+
+    def _density_grid_shape(self):
+        """the shape of the dense density grid -- read off the world size for a TensoRF density (no bake just for a shape)"""
+        if self._has_tensorf(self.density):
+            return torch.Size([1, 1] + [int(x) for x in self.world_size_density])
+        return self.density.get_dense_grid().shape
 
     # -- the contracted models' sample table -------------------------------------------------------------------
     def _sample_table(self, stepsize):
@@ -128,7 +140,7 @@ class TrainModel(nn.Module):
     # -- the native step ---------------------------------------------------------------------------------------
     def _can_fuse(self, rays_o):
         """the fused sampling ops need fast_color_thres > 0, like the reference's own masking branches"""
-        return self.fused_forward and self.fast_color_thres > 0 and rays_o.is_cuda
+        return self.fused_forward and self.fast_color_thres > 0 and rays_o.is_cuda and not self._has_tensorf()
 
     def _native_params(self):
         """The parameters of native_step.VoxGOStep (density grid, k0 grid, the rgbnet's three weights and biases), or None when this
@@ -138,7 +150,7 @@ class TrainModel(nn.Module):
         The coarse stage -- no rgbnet, the colour is the 3-channel k0 itself -- takes the native step only where `native_coarse` asks
         for it: the two grids followed by six None (VoxGOStep colour 'none').  The residual-colour rgbnet (rgbnet_direct = False) takes it
         only where `native_residual` asks for it, under the conditions of the direct one plus a k0 of >= 4 channels (colour 'residual')."""
-        if not (self.native_step and torch.is_grad_enabled()):
+        if not (self.native_step and torch.is_grad_enabled()) or self._has_tensorf():
             return None
         if self.rgbnet is None:
             if not (self.native_coarse and self._native_coarse_ok and self.k0.grid.shape[1] == 3):

@@ -124,6 +124,7 @@ def train_iteration(model, optimizer, rays_o, rays_d, viewdirs, target, cfg_trai
     tv_on = (global_step < _get(cfg_train, 'tv_before', 0) and global_step > _get(cfg_train, 'tv_after', 0)
              and global_step % _get(cfg_train, 'tv_every', 1) == 0)
     tv_terms = None
+    tensorf_tv = []
     if tv_on:
         # run_train.py:281-287.  The TV term is applied to the gradient the optimizer is about to use -- inside
         # optimizer.step, i.e. AFTER the cross-rank reduction in data-parallel runs (in a single process that is exactly
@@ -136,13 +137,20 @@ def train_iteration(model, optimizer, rays_o, rays_d, viewdirs, target, cfg_trai
         def tv_weight(base, which, ws):      # a float, or (wx, wy, wz) from the model's hook
             hook_ = getattr(model, 'tv_axis_weights', None)
             return hook_(base, which) if hook_ is not None else float(base * ws.max() / 128)
-        if _get(cfg_train, 'weight_tv_density', 0.0) > 0:
+        # a TensoRF grid (grid.TensoRFGrid: six factors, no `.grid`) stays out of the optimizer's TV pass and of _gradpool: its term
+        # is the model's own hook, called after backward() and before optimizer.step() like run_train.py:281-287
+        from .grid import TensoRFGrid
+        if _get(cfg_train, 'weight_tv_density', 0.0) > 0 and isinstance(model.density, TensoRFGrid):
+            tensorf_tv.append((model.density_total_variation_add_grad, _get(cfg_train, 'weight_tv_density') / n_global, dense))
+        elif _get(cfg_train, 'weight_tv_density', 0.0) > 0:
             tv_terms[model.density.grid] = (tv_weight(_get(cfg_train, 'weight_tv_density') / n_global, 'density', model.world_size_density),
                                             dense, model.density.tv_module)
-        if _get(cfg_train, 'weight_tv_k0', 0.0) > 0:
+        if _get(cfg_train, 'weight_tv_k0', 0.0) > 0 and isinstance(model.k0, TensoRFGrid):
+            tensorf_tv.append((model.k0_total_variation_add_grad, _get(cfg_train, 'weight_tv_k0') / n_global, dense))
+        elif _get(cfg_train, 'weight_tv_k0', 0.0) > 0:
             tv_terms[model.k0.grid] = (tv_weight(_get(cfg_train, 'weight_tv_k0') / n_global, 'k0', model.world_size_rgb),
                                        dense, model.k0.tv_module)
-    overlap = bool(tv_terms and overlap_k0_update and world_size == 1 and model.k0.grid in tv_terms)
+    overlap = bool(tv_terms and overlap_k0_update and world_size == 1 and hasattr(model.k0, 'grid') and model.k0.grid in tv_terms)
     hook = None
     if overlap and hasattr(optimizer, 'step_param') and hasattr(model.k0.grid, 'register_post_accumulate_grad_hook'):
         # the k0 update (the step's largest pass, HBM-bound) is queued on the second stream THE MOMENT the k0 gradient is
@@ -176,6 +184,8 @@ def train_iteration(model, optimizer, rays_o, rays_d, viewdirs, target, cfg_trai
             if hook is not None:
                 hook.remove()
         _mark(timers, "backward")
+        for tv_hook, tv_w, tv_dense in tensorf_tv:
+            tv_hook(tv_w, tv_dense)
         if overlap:
             optimizer.step(tv_terms=tv_terms, overlap=[model.k0.grid])     # (k0 is skipped here when the hook has updated it)
         elif tv_terms:

@@ -39,13 +39,23 @@ class _VoxGOBase(TrainModel):
                                 # TrainModel.native_residual = True: DirectVoxGO with rgbnet_direct = False too)
 
     def _init_grids(self, density_type, k0_type, density_config, k0_config, k0_dim, channels_last):
-        if density_type != 'DenseGrid' or k0_type != 'DenseGrid':
-            raise NotImplementedError("only DenseGrid (TensoRFGrid is outside the hot path, SURVEY.md section 8)")
+        # each grid is a dense one (grid.FourierGrid without levels) or a TensoRF one (grid.TensoRFGrid), independently, as
+        # grid.create_grid of the reference dispatches (dvgo.py:66-77, dcvgo.py:69-80); anything else: NotImplementedError
+        for t in (density_type, k0_type):
+            if t not in ('DenseGrid', 'TensoRFGrid'):
+                raise NotImplementedError(t)
         self.density_type, self.k0_type = density_type, k0_type
         self.density_config, self.k0_config = density_config, k0_config
-        self.density = self._make_grid(1, self.world_size, False, None)
+        self.density = self._make_typed_grid(density_type, 1, density_config, None)
         self.k0_dim = k0_dim
-        self.k0 = self._make_grid(k0_dim, self.world_size, False, channels_last)
+        self.k0 = self._make_typed_grid(k0_type, k0_dim, k0_config, channels_last)
+
+    def _make_typed_grid(self, grid_type, channels, config, channels_last):
+        if grid_type == 'DenseGrid':
+            return self._make_grid(channels, self.world_size, False, channels_last)
+        g = _grid.TensoRFGrid(channels=channels, world_size=self.world_size, xyz_min=self.xyz_min, xyz_max=self.xyz_max, config=config)
+        g.query_fn, g.tv_module = getattr(self._be, 'tensorf_query', None), getattr(self._be, 'tensorf_tv', None)
+        return g
 
     def _set_grid_resolution(self, num_voxels):
         self.num_voxels = num_voxels
@@ -179,6 +189,9 @@ class DirectVoxGO(_VoxGOBase):
     @torch.no_grad()
     def maskout_near_cam_vox(self, cam_o, near_clip):
         """density = -100 at the grid vertices closer than near_clip to any camera centre (dvgo.py:166-180)"""
+        if self._has_tensorf(self.density):
+            raise NotImplementedError("maskout_near_cam_vox writes density.grid: a TensoRFGrid density has none (the reference fails here "
+                                      "too; only the dense coarse stage calls it)")
         xyz = self._vertices(self.world_size.tolist())
         nearest = torch.stack([(xyz.unsqueeze(-2) - co.to(xyz.device)).pow(2).sum(-1).sqrt().amin(-1) for co in cam_o.split(100)]).amin(0)
         self.density.get_dense_grid()
@@ -306,7 +319,7 @@ class DirectContractedVoxGO(_VoxGOBase):
     def update_occupancy_cache_lt_nviews(self, rays_o_tr, rays_d_tr, imsz, render_kwargs, maskout_lt_nviews):
         """mask &= (voxel seen by at least maskout_lt_nviews training views)  (dcvgo.py:194-214)"""
         dev = self.xyz_min.device
-        count = torch.zeros(self.density.get_dense_grid().shape, dtype=torch.long, device=dev)
+        count = torch.zeros(self._density_grid_shape(), dtype=torch.long, device=dev)
         for o_img, d_img in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
             ones = torch.zeros([1, 1] + self.world_size.tolist(), device=dev).requires_grad_(True)
             for o, d in zip(o_img.split(8192), d_img.split(8192)):
