@@ -577,6 +577,32 @@ int ugrid_train_sample_compact_vox(int64_t n_rays, int32_t slots_per_ray, float 
                                    float *alpha2, float *weights2, int64_t *ray_id2, int64_t *step_id2, float *t2,
                                    uint8_t *inner2, ugrid_stream_t stream);
 
+/* ugrid_train_sample_dvgo / _dcvgo over a TensoRF (vector-matrix) DENSITY (grid.py:90-201 of the reference, channels == 1): the
+ * argument lists of those two with `density_grid, X, Y, Z` replaced by the six factors in the order xy_plane [1,Rxy,X,Y],
+ * xz_plane [1,R,X,Z], yz_plane [1,R,Y,Z], x_vec [1,R,X,1], y_vec [1,R,Y,1], z_vec [1,Rxy,Z,1] and X, Y, Z, R (n_comp), Rxy (n_comp_xy),
+ * comp_last (0: canonical, 1: the six stored component-last, as ugrid_tensorf_query takes them).  The same march, point for point --
+ * ray set-up, mask cache, Raw2Alpha, both thresholds, the stage-2 recurrence, the scratch slots and counts -- with the factorised
+ * lookup in place of the eight-corner gather: the density written is, bit for bit, what ugrid_tensorf_query (C = 1) returns at the
+ * point written.  ugrid_train_sample_compact_vox and ugrid_train_sample_backward follow unchanged; the density gradient [M1] they
+ * produce goes to ugrid_tensorf_query_backward over the M1 stage-1 points.  3 x R x 6 loads per kept sample (8 for a dense grid).
+ * hipErrorInvalidValue, before any launch: a NULL factor, R < 1, Rxy < 1 or a dimension < 1; n_rays <= 0: nothing to do, 0. */
+int ugrid_train_sample_dcvgo_tensorf(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                                     const float *y_vec, const float *z_vec, int X, int Y, int Z, int R, int Rxy, int comp_last,
+                                     const float *rays_o, const float *rays_d, int64_t n_rays, const float *t_table, int32_t n_samples,
+                                     const float *scene_center3, const float *scene_radius3, const float *xyz_min, const float *xyz_max,
+                                     double bg_len, int norm_l2, float dist_thres, const uint8_t *mask, const int32_t *mask_dims3,
+                                     const float *xyz2ijk_scale3, const float *xyz2ijk_shift3, float act_shift, float interval,
+                                     float thres, float *scratch_pts, float *scratch_density, int32_t *scratch_step, float *scratch_w,
+                                     float *scratch_T, int32_t *count, int32_t *count2, float *alphainv_last, ugrid_stream_t stream);
+int ugrid_train_sample_dvgo_tensorf(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                                    const float *y_vec, const float *z_vec, int X, int Y, int Z, int R, int Rxy, int comp_last,
+                                    const float *rays_o, const float *rays_d, int64_t n_rays, int32_t slots_per_ray,
+                                    const float *xyz_min, const float *xyz_max, float near, float far, float stepdist,
+                                    const uint8_t *mask, const int32_t *mask_dims3, const float *xyz2ijk_scale3,
+                                    const float *xyz2ijk_shift3, float act_shift, float interval, float thres, float *scratch_pts,
+                                    float *scratch_density, int32_t *scratch_step, float *scratch_w, float *scratch_T, int32_t *count,
+                                    int32_t *count2, float *alphainv_last, ugrid_stream_t stream);
+
 /* NEW (round 5; no reference counterpart): ONE training step's forward and backward of the reference's two dense-grid models
  * issued natively -- DirectVoxGO.forward (dvgo.py:332-425) / DirectContractedVoxGO.forward (dcvgo.py:265-384) /
  * FourierGridModel.forward (FourierGrid_model.py:554-672) with the default

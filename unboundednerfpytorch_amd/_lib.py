@@ -191,6 +191,10 @@ _SIGNATURES = {
     "ugrid_tensorf_query_backward": (_I, [_P] * 8 + [_I] * 7 + [_P, _P, _P, _L] + [_P] * 8),
     "ugrid_tensorf_tv_add_grad": (_I, [_P] * 12 + [_I] * 6 + [_F, _F, _F, _P]),
     "ugrid_tensorf_bake": (_I, [_P] * 7 + [_I] * 8 + [_P, _P]),
+    # (ugrid_train_sample_dcvgo / _dvgo with the six factors + X, Y, Z, R, Rxy, comp_last in place of the dense grid + X, Y, Z)
+    "ugrid_train_sample_dcvgo_tensorf": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _L, _P, _c.c_int32, _P, _P, _P, _P, _c.c_double, _I, _F, _P, _P, _P, _P,
+                                               _F, _F, _F] + [_P] * 9),
+    "ugrid_train_sample_dvgo_tensorf": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _L, _c.c_int32, _P, _P, _F, _F, _F, _P, _P, _P, _P, _F, _F, _F] + [_P] * 9),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

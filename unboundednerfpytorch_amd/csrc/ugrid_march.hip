@@ -2,6 +2,7 @@
 // Built with -fno-slp-vectorize (see ugrid_render.h header note and csrc/build.sh).
 #include "ugrid_render.h"
 #include "ugrid_rays.h"
+#include "ugrid_tensorf.h"
 
 // ----------------------------------------------------------------------------------------------
 // brick packing: canonical [P,C,X,Y,Z] -> [P*(X-1)(Y-1)(Z-1)] cell records of [H halves][8][CH]
@@ -548,15 +549,32 @@ k_train_march(ug_train_args a, const float *__restrict__ grid, const float *__re
   }
 }
 
+// The density source of the march below: the eight corners of a dense [X,Y,Z] grid, or the six factors of a TensoRF grid
+// (ugrid_tensorf.h: tf_density, the function k_tensorf_query calls -- 3 groups x Rg components x (4 plane + 2 vector) loads).
+struct ug_dens_dense { const float *__restrict__ grid; };
+template <bool CL> struct ug_dens_tensorf { const tf_factors &f; };
+__device__ __forceinline__ float ug_train_density(const ug_train_args &a, const ug_dens_dense &s, float ux, float uy, float uz) {
+  const ug_taps tp = ug_tap_setup_ld(a.X, a.Y, a.Z, ux, uy, uz);
+  float acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) acc += s.grid[tp.off[c]] * tp.w[c];
+  return acc;
+}
+template <bool CL>
+__device__ __forceinline__ float ug_train_density(const ug_train_args &, const ug_dens_tensorf<CL> &s, float ux, float uy, float uz) {
+  return tf_density<CL>(s.f, ux, uy, uz);
+}
+
 // k_train_march<true> for the dense-grid models (ug_train_vox above): MODE 1 = DirectContractedVoxGO, 2 = DirectVoxGO, 3 = DirectMPIGO.
-// Same slot / scratch contract and the same stage-2 recurrence; P = 1, F = 0.
-template <int MODE>
-__global__ void __launch_bounds__(256)
-k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ grid, const float *__restrict__ rays_o,
-                  const float *__restrict__ rays_d, const float *__restrict__ t_table, const float *__restrict__ xyz_min,
-                  const float *__restrict__ xyz_max, float *__restrict__ s_pts, float *__restrict__ s_dens,
-                  int32_t *__restrict__ s_step, int32_t *__restrict__ count, float *__restrict__ s_w, float *__restrict__ s_T,
-                  int32_t *__restrict__ count2, float *__restrict__ alphainv_last) {
+// Same slot / scratch contract and the same stage-2 recurrence; P = 1, F = 0.  One body for both density sources (DENS): the kernels
+// below only name their arguments.  No workgroup barrier and no LDS: waves past n_rays return at the top and leave the loop on their own.
+template <int MODE, class DENS>
+__device__ __forceinline__ void
+ug_train_march_vox(const ug_train_args &a, const ug_train_vox &v, const DENS &src, const float *__restrict__ rays_o,
+                   const float *__restrict__ rays_d, const float *__restrict__ t_table, const float *__restrict__ xyz_min,
+                   const float *__restrict__ xyz_max, float *__restrict__ s_pts, float *__restrict__ s_dens,
+                   int32_t *__restrict__ s_step, int32_t *__restrict__ count, float *__restrict__ s_w, float *__restrict__ s_T,
+                   int32_t *__restrict__ count2, float *__restrict__ alphainv_last) {
   const int64_t ray = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (ray >= a.n_rays) return;
   const int lane = ug_lane();
@@ -625,10 +643,7 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
     if (keep) keep = ug_mask_lookup(v, px, py, pz);
     if (keep) {
       const float ux = ug_unorm(px, lox, hix), uy = ug_unorm(py, loy, hiy), uz = ug_unorm(pz, loz, hiz);
-      const ug_taps tp = ug_tap_setup_ld(a.X, a.Y, a.Z, ux, uy, uz);
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) acc += grid[tp.off[c]] * tp.w[c];
+      const float acc = ug_train_density(a, src, ux, uy, uz);
       dens = acc;
       if (MODE == 3) {
         // act_shift(p), restated from ug_march_tile_mpi (ugrid_render.h: "act_shift: uz in [-1, 1] ..."): v0 * w0 + v1 * w1 as
@@ -681,6 +696,31 @@ k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ gri
     count2[ray] = kept2;
     alphainv_last[ray] = T_cum;
   }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256)
+k_train_march_vox(ug_train_args a, ug_train_vox v, const float *__restrict__ grid, const float *__restrict__ rays_o,
+                  const float *__restrict__ rays_d, const float *__restrict__ t_table, const float *__restrict__ xyz_min,
+                  const float *__restrict__ xyz_max, float *__restrict__ s_pts, float *__restrict__ s_dens,
+                  int32_t *__restrict__ s_step, int32_t *__restrict__ count, float *__restrict__ s_w, float *__restrict__ s_T,
+                  int32_t *__restrict__ count2, float *__restrict__ alphainv_last) {
+  ug_train_march_vox<MODE>(a, v, ug_dens_dense{grid}, rays_o, rays_d, t_table, xyz_min, xyz_max, s_pts, s_dens, s_step, count, s_w, s_T, count2,
+                           alphainv_last);
+}
+
+// the same march over a TensoRF density (MODE 1 / 2; CL: component-last factors): tf_density in place of the eight-corner gather, and
+// everything else -- ray set-up, mask cache, alpha, threshold, stage 2, the scratch slots -- the code above, so that the compaction
+// and the backward of the dense march serve it unchanged
+template <int MODE, bool CL>
+__global__ void __launch_bounds__(256)
+k_train_march_tensorf(ug_train_args a, ug_train_vox v, tf_factors f, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                      const float *__restrict__ t_table, const float *__restrict__ xyz_min, const float *__restrict__ xyz_max,
+                      float *__restrict__ s_pts, float *__restrict__ s_dens, int32_t *__restrict__ s_step, int32_t *__restrict__ count,
+                      float *__restrict__ s_w, float *__restrict__ s_T, int32_t *__restrict__ count2, float *__restrict__ alphainv_last) {
+  static_assert(MODE == 1 || MODE == 2, "TensoRF densities: DirectContractedVoxGO and DirectVoxGO");
+  ug_train_march_vox<MODE>(a, v, ug_dens_tensorf<CL>{f}, rays_o, rays_d, t_table, xyz_min, xyz_max, s_pts, s_dens, s_step, count, s_w, s_T,
+                           count2, alphainv_last);
 }
 
 // after the two cumsums: one wave per ray copies its slot to the ray-major arrays of stage 1 (M1 samples: what the backward
@@ -921,6 +961,80 @@ extern "C" int ugrid_train_sample_dvgo(const float *density_grid, int X, int Y, 
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_vox<2>), dim3(ug_blocks(n_rays * UG_WAVE, 256)), dim3(256), 0, ST(s), a, v, density_grid,
                      rays_o, rays_d, (const float *)nullptr, xyz_min, xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w,
                      scratch_T, count2, alphainv_last);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the TensoRF twins of the two entry points above: the six factors in place of the dense grid
+static bool ug_tensorf_density_ok(const float *xy, const float *xz, const float *yz, const float *xv, const float *yv, const float *zv, int X,
+                                  int Y, int Z, int R, int Rxy) {
+  return xy && xz && yz && xv && yv && zv && X >= 1 && Y >= 1 && Z >= 1 && R >= 1 && Rxy >= 1;
+}
+
+extern "C" int ugrid_train_sample_dcvgo_tensorf(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                                                const float *y_vec, const float *z_vec, int X, int Y, int Z, int R, int Rxy, int comp_last,
+                                                const float *rays_o, const float *rays_d, int64_t n_rays, const float *t_table,
+                                                int32_t n_samples, const float *scene_center3, const float *scene_radius3,
+                                                const float *xyz_min, const float *xyz_max, double bg_len, int norm_l2, float dist_thres,
+                                                const uint8_t *mask, const int32_t *mask_dims3, const float *xyz2ijk_scale3,
+                                                const float *xyz2ijk_shift3, float act_shift, float interval, float thres, float *scratch_pts,
+                                                float *scratch_density, int32_t *scratch_step, float *scratch_w, float *scratch_T,
+                                                int32_t *count, int32_t *count2, float *alphainv_last, ugrid_stream_t s) {
+  if (!ug_tensorf_density_ok(xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, X, Y, Z, R, Rxy)) return (int)hipErrorInvalidValue;
+  if (n_rays <= 0) return 0;
+  if (n_samples <= 0 || !scratch_w || !scratch_T || !count2 || !alphainv_last || !t_table) return (int)hipErrorInvalidValue;
+  ug_train_vox v;
+  const int rc = ug_fill_train_vox(&v, mask, mask_dims3, xyz2ijk_scale3, xyz2ijk_shift3);
+  if (rc) return rc;
+  v.dist_thres = dist_thres;
+  ug_train_args a;
+  a.n_rays = n_rays; a.S = n_samples; a.P = 1; a.F = 0; a.X = X; a.Y = Y; a.Z = Z; a.norm_l2 = norm_l2;
+  a.cx = scene_center3[0]; a.cy = scene_center3[1]; a.cz = scene_center3[2];
+  a.rx = scene_radius3[0]; a.ry = scene_radius3[1]; a.rz = scene_radius3[2];
+  const double Bd = 1.0 + bg_len;
+  a.B = (float)Bd; a.A = (float)bg_len;       // dcvgo.py:261: (1 + bg_len) - bg_len / norm
+  a.shift = act_shift; a.interval = interval; a.thres = thres;
+  const tf_factors f = tf_make(xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, X, Y, Z, R, Rxy);
+  const dim3 blocks(ug_blocks(n_rays * UG_WAVE, 256));
+  if (comp_last)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_tensorf<1, true>), blocks, dim3(256), 0, ST(s), a, v, f, rays_o, rays_d, t_table, xyz_min,
+                       xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w, scratch_T, count2, alphainv_last);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_tensorf<1, false>), blocks, dim3(256), 0, ST(s), a, v, f, rays_o, rays_d, t_table, xyz_min,
+                       xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w, scratch_T, count2, alphainv_last);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_train_sample_dvgo_tensorf(const float *xy_plane, const float *xz_plane, const float *yz_plane, const float *x_vec,
+                                               const float *y_vec, const float *z_vec, int X, int Y, int Z, int R, int Rxy, int comp_last,
+                                               const float *rays_o, const float *rays_d, int64_t n_rays, int32_t slots_per_ray,
+                                               const float *xyz_min, const float *xyz_max, float near, float far, float stepdist,
+                                               const uint8_t *mask, const int32_t *mask_dims3, const float *xyz2ijk_scale3,
+                                               const float *xyz2ijk_shift3, float act_shift, float interval, float thres, float *scratch_pts,
+                                               float *scratch_density, int32_t *scratch_step, float *scratch_w, float *scratch_T,
+                                               int32_t *count, int32_t *count2, float *alphainv_last, ugrid_stream_t s) {
+  if (!ug_tensorf_density_ok(xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, X, Y, Z, R, Rxy)) return (int)hipErrorInvalidValue;
+  if (n_rays <= 0) return 0;
+  if (slots_per_ray <= 0 || !(stepdist > 0.f) || !scratch_w || !scratch_T || !count2 || !alphainv_last) return (int)hipErrorInvalidValue;
+  ug_train_vox v;
+  const int rc = ug_fill_train_vox(&v, mask, mask_dims3, xyz2ijk_scale3, xyz2ijk_shift3);
+  if (rc) return rc;
+  v.near = near; v.far = far; v.stepdist = stepdist;
+  ug_train_args a;
+  a.n_rays = n_rays; a.S = slots_per_ray; a.P = 1; a.F = 0; a.X = X; a.Y = Y; a.Z = Z; a.norm_l2 = 0;
+  a.cx = a.cy = a.cz = 0.f; a.rx = a.ry = a.rz = 1.f; a.B = 1.f; a.A = 0.f;
+  a.shift = act_shift; a.interval = interval; a.thres = thres;
+  const tf_factors f = tf_make(xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, X, Y, Z, R, Rxy);
+  const dim3 blocks(ug_blocks(n_rays * UG_WAVE, 256));
+  if (comp_last)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_tensorf<2, true>), blocks, dim3(256), 0, ST(s), a, v, f, rays_o, rays_d,
+                       (const float *)nullptr, xyz_min, xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w, scratch_T, count2,
+                       alphainv_last);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_train_march_tensorf<2, false>), blocks, dim3(256), 0, ST(s), a, v, f, rays_o, rays_d,
+                       (const float *)nullptr, xyz_min, xyz_max, scratch_pts, scratch_density, scratch_step, count, scratch_w, scratch_T, count2,
+                       alphainv_last);
   UG_LAUNCH_CHECK();
   return 0;
 }

@@ -5,10 +5,11 @@
   FourierGrid    drop-in for the reference's nn.Module of that name (FourierGrid_grid.py:43-103): same constructor,
                  parameter / buffer names (state_dict compatible) and methods
   MaskGrid       <- MaskGrid.forward (grid.py:230-239, FourierGrid_grid.py:159-168)
-  TrainMarch / TrainSample / TrainSampleVox
-                 the fused sampling of the training forwards as autograd ops.  The two sample ops differ in their input checks
-                 and their march entry point only: what follows the march (_sample_stages) and the backward are one piece of
-                 code, and every op -- native_step.VoxGOStep included -- takes its per-(ray, slot) scratch from scratch()"""
+  TrainMarch / TrainSample / TrainSampleVox / TrainSampleTensoRF
+                 the fused sampling of the training forwards as autograd ops.  The sample ops differ in their input checks
+                 and their march entry point only (TrainSampleTensoRF, over a factorised density, also in the lookup's backward):
+                 what follows the march (_sample_stages) and the sampling's backward are one piece of code, and every op --
+                 native_step.VoxGOStep included -- takes its per-(ray, slot) scratch from scratch()"""
 import torch
 import torch.nn.functional as F
 
@@ -239,71 +240,82 @@ class TrainSampleVox(TrainSample):
 
     @staticmethod
     def forward(ctx, grid, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg):
-        import ctypes
         _lib.wait_pending(grid)
-        _lib.require_cuda(("grid", grid), ("rays_o", rays_o), ("rays_d", rays_d), ("xyz_min", xyz_min), ("xyz_max", xyz_max), ("mask", mask))
-        _lib.require_f32(("grid", grid), ("rays_o", rays_o), ("rays_d", rays_d))
+        _lib.require_cuda(("grid", grid))
+        _lib.require_f32(("grid", grid))
         if grid.dim() != 5 or grid.shape[0] != 1 or grid.shape[1] != 1 or not grid.is_contiguous():
             raise RuntimeError("density grid must be a contiguous [1,1,X,Y,Z]")
-        if mask.dtype != torch.bool or mask.dim() != 3 or not mask.is_contiguous():
-            raise RuntimeError("mask must be a contiguous bool [mi,mj,mk]")
-        mode = cfg['mode']
-        _, _, X, Y, Z = grid.shape
-        R = rays_o.shape[0]
-        if mode == 'dcvgo':
-            _lib.require_cuda(("t", t))
-            _lib.require_f32(("t", t))
-            S = t.numel()
-        elif mode == 'dvgo':
-            S = int(cfg['slots'])
-        elif mode == 'mpi':
-            S, D = int(cfg['n_steps']), int(cfg['mpi_depth'])
-            tab = cfg['act_shift']
-            _lib.require_cuda(("act_shift", tab))
-            _lib.require_f32(("act_shift", tab))
-            if S < 2 or not 1 <= D <= 256 or tab.numel() != D or not tab.is_contiguous() or tab.device != grid.device:
-                raise RuntimeError("mpi: n_steps >= 2, 1 <= mpi_depth <= 256 and a contiguous act_shift of mpi_depth values on the grid's device")
-        else:
-            raise ValueError(mode)
-        f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
-        md = (ctypes.c_int32 * 3)(*[int(x) for x in mask.shape])
-        ms, mh = f3(cfg['mask_scale']), f3(cfg['mask_shift'])
-        vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        consts = (0.0 if mode == 'mpi' else float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres']))
-        if mode == 'dcvgo':
-            c3, r3 = f3(cfg['scene_center']), f3(cfg['scene_radius'])
+        R, S, consts, march = _vox_march((_lib.ptr(grid), *grid.shape[2:]), "", grid.device, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg)
+        return _sample_stages(ctx, grid, R, S, t if cfg['mode'] == 'dcvgo' else None, xyz_min, xyz_max, consts, 0, march, vox=True)
 
-            def march(*outs):
-                _lib.check(_L.ugrid_train_sample_dcvgo(
-                    _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, _lib.ptr(t), S, vp(c3), vp(r3), _lib.ptr(xyz_min),
-                    _lib.ptr(xyz_max), float(cfg['bg_len']), int(bool(cfg['norm_l2'])), float(cfg['dist_thres']), _lib.ptr(mask), vp(md),
-                    vp(ms), vp(mh), *consts, *outs), "train_sample_dcvgo")
-        elif mode == 'mpi':
-            def march(*outs):
-                _lib.check(_L.ugrid_train_sample_mpi(
-                    _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max), _lib.ptr(tab), D,
-                    _lib.ptr(mask), vp(md), vp(ms), vp(mh), consts[1], consts[2], *outs), "train_sample_mpi")
-        else:
-            def march(*outs):
-                _lib.check(_L.ugrid_train_sample_dvgo(
-                    _lib.ptr(grid), X, Y, Z, _lib.ptr(rays_o), _lib.ptr(rays_d), R, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-                    float(cfg['near']), float(cfg['far']), float(cfg['stepdist']), _lib.ptr(mask), vp(md), vp(ms), vp(mh), *consts,
-                    *outs), "train_sample_dvgo")
-        return _sample_stages(ctx, grid, R, S, t if mode == 'dcvgo' else None, xyz_min, xyz_max, consts, 0, march, vox=True)
+
+def _vox_march(density_args, suffix, dev, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg):
+    """What TrainSampleVox and TrainSampleTensoRF share behind the checks of their density: the checks of the rays, the mask and the
+    mode's own inputs, and the march entry point ugrid_train_sample_<mode><suffix> bound to everything but its outputs.
+    density_args: what that entry point takes for the density (grid pointer, X, Y, Z; suffix "_tensorf": the six factor pointers, X,
+    Y, Z, R, Rxy, comp_last -- 'dvgo' and 'dcvgo' only); dev: the density's device.  -> R, S (scratch slots per ray), consts (shift,
+    interval, thres), march(*pointers of the scratch, the counts and alphainv_last, stream)"""
+    import ctypes
+    _lib.require_cuda(("rays_o", rays_o), ("rays_d", rays_d), ("xyz_min", xyz_min), ("xyz_max", xyz_max), ("mask", mask))
+    _lib.require_f32(("rays_o", rays_o), ("rays_d", rays_d))
+    if mask.dtype != torch.bool or mask.dim() != 3 or not mask.is_contiguous():
+        raise RuntimeError("mask must be a contiguous bool [mi,mj,mk]")
+    mode = cfg['mode']
+    R = rays_o.shape[0]
+    if mode == 'dcvgo':
+        _lib.require_cuda(("t", t))
+        _lib.require_f32(("t", t))
+        S = t.numel()
+    elif mode == 'dvgo':
+        S = int(cfg['slots'])
+    elif mode == 'mpi' and not suffix:
+        S, D = int(cfg['n_steps']), int(cfg['mpi_depth'])
+        tab = cfg['act_shift']
+        _lib.require_cuda(("act_shift", tab))
+        _lib.require_f32(("act_shift", tab))
+        if S < 2 or not 1 <= D <= 256 or tab.numel() != D or not tab.is_contiguous() or tab.device != dev:
+            raise RuntimeError("mpi: n_steps >= 2, 1 <= mpi_depth <= 256 and a contiguous act_shift of mpi_depth values on the grid's device")
+    else:
+        raise ValueError(mode)
+    f3 = lambda v: (ctypes.c_float * 3)(*[float(x) for x in v])
+    md = (ctypes.c_int32 * 3)(*[int(x) for x in mask.shape])
+    ms, mh = f3(cfg['mask_scale']), f3(cfg['mask_shift'])
+    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    consts = (0.0 if mode == 'mpi' else float(cfg['act_shift']), float(cfg['interval']), float(cfg['thres']))
+    rays = (_lib.ptr(rays_o), _lib.ptr(rays_d), R)
+    mask_args = (_lib.ptr(mask), vp(md), vp(ms), vp(mh))
+    host = [md, ms, mh]          # (the host arrays behind the pointers live as long as `march`)
+    if mode == 'dcvgo':
+        c3, r3 = f3(cfg['scene_center']), f3(cfg['scene_radius'])
+        host += [c3, r3]
+        args = (*rays, _lib.ptr(t), S, vp(c3), vp(r3), _lib.ptr(xyz_min), _lib.ptr(xyz_max), float(cfg['bg_len']), int(bool(cfg['norm_l2'])),
+                float(cfg['dist_thres']), *mask_args, *consts)
+    elif mode == 'mpi':
+        args = (*rays, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max), _lib.ptr(tab), D, *mask_args, consts[1], consts[2])
+    else:
+        args = (*rays, S, _lib.ptr(xyz_min), _lib.ptr(xyz_max), float(cfg['near']), float(cfg['far']), float(cfg['stepdist']), *mask_args, *consts)
+    fn, what = getattr(_L, "ugrid_train_sample_%s%s" % (mode, suffix)), "train_sample_%s%s" % (mode, suffix)
+
+    def march(*outs, _host=host):
+        _lib.check(fn(*density_args, *args, *outs), what)
+    return R, S, consts, march
 
 
 def _sample_stages(ctx, grid, R, S, t, xyz_min, xyz_max, consts, freq_num, march, vox):
-    """What TrainSample and TrainSampleVox do after their input checks: the scratch, `march(*pointers of the scratch, the two
-    per-ray counts and alphainv_last, stream)` -- the caller's march entry point --, the cumsum and the ONE host read (M1, M2),
-    the stage-1 / stage-2 arrays, the compaction (`vox`: ugrid_train_sample_compact_vox, which also writes the inner flags of
-    the samples when there is a sample table `t`), and what the shared backward reads from ctx."""
-    dev = grid.device
+    """What TrainSample, TrainSampleVox and TrainSampleTensoRF do after their input checks: the scratch, `march(*pointers of the
+    scratch, the two per-ray counts and alphainv_last, stream)` -- the caller's march entry point --, the cumsum and the ONE host
+    read (M1, M2), the stage-1 / stage-2 arrays, the compaction (`vox`: ugrid_train_sample_compact_vox, which also writes the inner
+    flags of the samples when there is a sample table `t`), and what the backwards read from ctx: the stage-1 arrays and
+    ctx.consts always; of the density parameter -- `grid`: the 5-D grid, or the six factors of a TensoRF density -- the dense
+    backward's shape, strides and gradient-pool key for a grid, nothing for factors (their op saves them itself)."""
+    dense = torch.is_tensor(grid)
+    dev = grid.device if dense else grid[0].device
     sc = scratch(dev, R * S)
     counts = torch.empty(2, R, dtype=torch.int32, device=dev)
     ainv = torch.empty(R, device=dev)
     shift, interval, thres = consts
     with _lib.guard(dev):
-        st = _lib.stream_of(grid)
+        st = _lib.stream_of(ainv)
         march(*[_lib.ptr(x) for x in sc], _lib.ptr(counts[0]), _lib.ptr(counts[1]), _lib.ptr(ainv), st)
         off = torch.cumsum(counts, 1, dtype=torch.int64)            # [2,R] inclusive
         M1, M2 = (int(x) for x in off[:, -1].tolist()) if R > 0 else (0, 0)     # the one host read
@@ -324,9 +336,11 @@ def _sample_stages(ctx, grid, R, S, t, xyz_min, xyz_max, consts, freq_num, march
                            "train_sample_compact_vox")
             else:
                 _lib.check(_L.ugrid_train_sample_compact(*args, st), "train_sample_compact")
-    ctx.save_for_backward(pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max)
-    ctx.shape, ctx.freq_num, ctx.consts = tuple(grid.shape), freq_num, (shift, interval)
-    ctx.pool_key, ctx.grid_stride = _gradpool.key_of(grid), tuple(grid.stride())
+    ctx.save_for_backward(pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max, *(() if dense else grid))
+    ctx.freq_num, ctx.consts = freq_num, (shift, interval)
+    if dense:
+        ctx.shape = tuple(grid.shape)
+        ctx.pool_key, ctx.grid_stride = _gradpool.key_of(grid), tuple(grid.stride())
     ctx.mark_non_differentiable(pts2, alpha2, ray2, step2, tt2, *inner2)
     return (pts2, dens2, alpha2, w2, ainv, ray2, step2, tt2) + inner2
 
@@ -353,9 +367,6 @@ def _tensorf_args(factors, f_vec, world_size=None):
     xy, xz, yz, xv, yv, zv = factors
     named = list(zip(TENSORF_FACTORS, factors)) + ([("f_vec", f_vec)] if f_vec is not None else [])
     _lib.require_f32(*named)
-    for name, t in named:
-        if not t.is_cuda or t.device != xy.device:
-            raise RuntimeError("%s must be a CUDA tensor on the device of xy_plane" % name)
     if any(t.dim() != 4 or t.shape[0] != 1 for t in factors):
         raise RuntimeError("TensoRF factors are [1,R,A,B] planes and [1,R,N,1] vectors")
     Rxy, X, Y = xy.shape[1:]
@@ -369,6 +380,9 @@ def _tensorf_args(factors, f_vec, world_size=None):
     for name, t in zip(TENSORF_FACTORS, factors):
         if not (t.is_contiguous(memory_format=torch.channels_last) if comp_last else t.is_contiguous()):
             raise RuntimeError("%s must be contiguous (the six factors share one layout, canonical or component-last)" % name)
+    for name, t in named:          # (after the shape and layout checks, which need no device)
+        if not t.is_cuda or t.device != xy.device:
+            raise RuntimeError("%s must be a CUDA tensor on the device of xy_plane" % name)
     C = 1
     if f_vec is not None:
         if f_vec.dim() != 2 or f_vec.shape[0] != R + R + Rxy or not f_vec.is_contiguous():
@@ -465,6 +479,48 @@ def tensorf_compose(factors, f_vec, xyz, xyz_min, xyz_max):
     if f_vec is None:
         return (feats[0].sum(-1) + feats[1].sum(-1) + feats[2].sum(-1)).reshape(xyz.shape[:-1])
     return torch.mm(torch.cat(feats, -1), f_vec).reshape(*xyz.shape[:-1], f_vec.shape[1])
+
+
+class TrainSampleTensoRF(torch.autograd.Function):
+    """TrainSampleVox for a TensoRF DENSITY (cfg['mode'] 'dvgo' or 'dcvgo'): the same march with the factorised lookup in place of
+    the eight-corner gather (include/ugrid_hip.h: ugrid_train_sample_dvgo_tensorf / _dcvgo_tensorf; the density it returns is, bit
+    for bit, tensorf_query's at the returned points), the same compaction, the same nine outputs.  The backward is
+    ugrid_train_sample_backward over the M1 stage-1 samples, then the factorised lookup's backward (ugrid_tensorf_query_backward)
+    over those M1 points only: six gradients, each in its factor's own layout (new tensors: TensoRF factors stay out of _gradpool).
+
+    forward(xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, rays_o [R,3], rays_d [R,3], t [S] or None, xyz_min, xyz_max,
+            mask [mi,mj,mk] bool, cfg) -- cfg as TrainSampleVox takes it for the mode."""
+
+    @staticmethod
+    def forward(ctx, xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg):
+        factors = (xy_plane, xz_plane, yz_plane, x_vec, y_vec, z_vec)
+        for p in factors:
+            _lib.wait_pending(p)
+        ptrs, dims, cl = _tensorf_args(factors, None)
+        R, S, consts, march = _vox_march((*ptrs[:6], *dims[:5], cl), "_tensorf", xy_plane.device, rays_o, rays_d, t, xyz_min, xyz_max, mask, cfg)
+        if any(x.device != xy_plane.device for x in (rays_o, rays_d, xyz_min, xyz_max, mask)):
+            raise RuntimeError("the factors, rays_o, rays_d, xyz_min, xyz_max and mask must be on the same device")
+        return _sample_stages(ctx, factors, R, S, t if cfg['mode'] == 'dcvgo' else None, xyz_min, xyz_max, consts, 0, march, vox=True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pts, g_dens2, g_alpha, g_w2, g_ainv, *g_rest):
+        pts1, dens1, w1, T1, pos2, counts, off, ainv, xyz_min, xyz_max, *factors = ctx.saved_tensors
+        dev = pts1.device
+        M1, R = pts1.shape[0], ainv.shape[0]
+        if M1 == 0:          # no sample took part in the forward: zero gradients, nothing launched
+            grads = [torch.zeros_like(p, memory_format=torch.preserve_format) for p in factors]
+        else:
+            f32 = lambda g: None if g is None else g.to(torch.float32).contiguous()
+            g_dens2, g_w2, g_ainv = f32(g_dens2), f32(g_w2), f32(g_ainv)
+            g1 = torch.empty(M1, device=dev)
+            with _lib.guard(dev):
+                _lib.check(_L.ugrid_train_sample_backward(R, ctx.consts[0], ctx.consts[1], _lib.ptr(dens1), _lib.ptr(w1), _lib.ptr(T1),
+                                                          _lib.ptr(pos2), _lib.ptr(counts[0]), _lib.ptr(off[0]), _lib.ptr(ainv),
+                                                          _lib.ptr(g_w2), _lib.ptr(g_ainv), _lib.ptr(g_dens2), _lib.ptr(g1),
+                                                          _lib.stream_of(pts1)), "train_sample_backward")
+            grads = tensorf_query_backward(g1, factors, None, pts1, xyz_min, xyz_max)[:6]
+        return tuple(grads) + (None,) * 7
 
 
 class TensoRFQuery(torch.autograd.Function):

@@ -42,6 +42,9 @@ class TrainModel(nn.Module):
     native_residual = False     # True: DirectVoxGO's residual-colour rgbnet (rgbnet_direct = False: rgbnet(k0[:, 3:], view) + k0[:, :3])
                                 # also takes native_step.VoxGOStep (colour 'residual'); the other models ignore it
     _native_residual_ok = False
+    fused_tensorf = False       # True: DirectVoxGO / DirectContractedVoxGO with a TensoRF density and / or k0 take the fused sampling too
+                                # (grid.TrainSampleTensoRF over a factorised density, grid.TrainSampleVox over a dense one) and behind
+                                # it the fused rgbnet and ops.RenderLoss; off until a measurement argues for it
 
     # -- construction helpers ------------------------------------------------------------------------------
     def _make_grid(self, channels, world_size, fourier, channels_last):
@@ -109,8 +112,8 @@ class TrainModel(nn.Module):
                                  stepsize, downrate, irregular_shape)
 
     def _has_tensorf(self, *grids):
-        """is one of `grids` (default: density and k0) a TensoRF grid?  Such a model takes the composed forward: there is no fused
-        sampling march and no native step over factorised grids"""
+        """is one of `grids` (default: density and k0) a TensoRF grid?  Such a model takes the composed forward unless `fused_tensorf`
+        asks for the fused sampling; there is no native step over factorised grids"""
         grids = grids or (getattr(self, 'density', None), getattr(self, 'k0', None))
         return any(isinstance(g, _grid.TensoRFGrid) for g in grids)
 
@@ -139,8 +142,21 @@ class TrainModel(nn.Module):
 
     # -- the native step ---------------------------------------------------------------------------------------
     def _can_fuse(self, rays_o):
-        """the fused sampling ops need fast_color_thres > 0, like the reference's own masking branches"""
-        return self.fused_forward and self.fast_color_thres > 0 and rays_o.is_cuda and not self._has_tensorf()
+        """the fused sampling ops need fast_color_thres > 0, like the reference's own masking branches; a model with a TensoRF grid
+        takes them only where `fused_tensorf` asks for it, and a TensoRF density only while the HIP lookup is its lookup (the march
+        computes tf_density: an injected query function would not be what it samples)"""
+        if not (self.fused_forward and self.fast_color_thres > 0 and rays_o.is_cuda):
+            return False
+        if not self._has_tensorf():
+            return True
+        return self.fused_tensorf and not (self._has_tensorf(self.density) and self.density.query_fn is not None)
+
+    def _fused_sample(self, rays_o, rays_d, t, cfg):
+        """the fused sampling op of this model's density type: the nine outputs of grid.TrainSampleVox"""
+        o, d = rays_o.contiguous(), rays_d.contiguous()
+        if self._has_tensorf(self.density):
+            return _grid.TrainSampleTensoRF.apply(*self.density.factors(), o, d, t, self.xyz_min, self.xyz_max, self.mask_cache.mask, cfg)
+        return _grid.TrainSampleVox.apply(self.density.grid, o, d, t, self.xyz_min, self.xyz_max, self.mask_cache.mask, cfg)
 
     def _native_params(self):
         """The parameters of native_step.VoxGOStep (density grid, k0 grid, the rgbnet's three weights and biases), or None when this

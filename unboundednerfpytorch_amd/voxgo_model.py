@@ -235,8 +235,7 @@ class DirectVoxGO(_VoxGOBase):
                 for k in ('raw_density', 'step_id', 't'):      # (not in DirectVoxGO's return dict, dvgo.py:405-417)
                     out.pop(k)
                 return out
-            pts, density, alpha, weights, alphainv_last, ray_id, step_id, tt, _ = _grid.TrainSampleVox.apply(
-                self.density.grid, rays_o.contiguous(), rays_d.contiguous(), None, self.xyz_min, self.xyz_max, self.mask_cache.mask, cfg)
+            pts, density, alpha, weights, alphainv_last, ray_id, step_id, tt, _ = self._fused_sample(rays_o, rays_d, None, cfg)
         else:
             tt = None
             pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, **render_kwargs)
@@ -366,8 +365,7 @@ class DirectContractedVoxGO(_VoxGOBase):
                                            self.mask_cache.mask)
                 out['n_max'] = n_max
                 return out
-            pts, density, alpha, weights, alphainv_last, ray_id, step_id, tt, inner = _grid.TrainSampleVox.apply(
-                self.density.grid, rays_o.contiguous(), rays_d.contiguous(), t, self.xyz_min, self.xyz_max, self.mask_cache.mask, cfg)
+            pts, density, alpha, weights, alphainv_last, ray_id, step_id, tt, inner = self._fused_sample(rays_o, rays_d, t, cfg)
         else:
             from . import ub360_utils_cuda
             pts, inner, t = self.sample_ray(ori_rays_o=rays_o, ori_rays_d=rays_d, is_train=global_step is not None, **render_kwargs)
