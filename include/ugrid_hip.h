@@ -784,6 +784,30 @@ int ugrid_tensorf_bake(const float *xy_plane, const float *xz_plane, const float
                        const float *y_vec, const float *z_vec, const float *f_vec, int X, int Y, int Z, int R, int Rxy,
                        int C, int comp_last, int out_channels_last, float *out, ugrid_stream_t stream);
 
+/* ------------------------------------------------------------------ frame assembly of the multi-GPU render path (csrc/ugrid_frame.hip)
+ * A packed frame is [H*W,5] fp32 = rgb(3), depth, alphainv_last per pixel, in image order.  Both entry points only move 32-bit
+ * words: every bit pattern (NaN payloads, -0.0) arrives unchanged.  32-bit index arithmetic: hipErrorInvalidValue, before anything
+ * touches the device, when 5*per, 5*world*per or 5*H*W exceeds INT32_MAX.
+ *
+ * frame_pack: a rank's send tile out [per,5]: rows 0..n from rgb [n,3] / depth [n] / last [n], rows n..per zero.  n = 0 is legal
+ * (the three pointers may then be NULL); per = 0 is a no-op.
+ *
+ * frame_assemble: out [H*W,5] from
+ *   gathered != NULL  the all-gathered tiles [world*per,5] (rgb / depth / last ignored), or
+ *   gathered == NULL  the three per-ray arrays of a single-device render (world / per / deal_group ignored).
+ * The source row of pixel (y, x) is computed, no index table is read:
+ *   ray position  tile8 = 0: q = y*W + x;  tile8 = 1 (H and W multiples of 8): the 8 x 8 pixel-block order, blocks row-major,
+ *                 q = ((y>>3)*(W>>3) + (x>>3))*64 + lane with lane bits y2 x2 y1 x1 y0 x0;
+ *   deal_group = 0  contiguous bands of `per` rows per rank (per = ceil(ceil(R/world)/64)*64): row = q;
+ *   deal_group >= 1  64-ray tiles dealt round-robin in groups of deal_group: t = q/64, g = t/deal_group,
+ *                 row = (g % world)*per + ((g / world)*deal_group + t % deal_group)*64 + q % 64, per >= rank 0's share.
+ * hipErrorInvalidValue too when a computed row could fall outside the buffer (world*per < H*W for bands, per below rank 0's share
+ * for a deal), and for tile8 with H or W not a multiple of 8. */
+int ugrid_frame_pack(const float *rgb, const float *depth, const float *last, int64_t n, int64_t per, float *out,
+                     ugrid_stream_t stream);
+int ugrid_frame_assemble(const float *gathered, const float *rgb, const float *depth, const float *last, int32_t H, int32_t W,
+                         int32_t world, int64_t per, int32_t deal_group, int32_t tile8, float *out, ugrid_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,8 @@ _SIGNATURES = {
     "ugrid_train_sample_dcvgo_tensorf": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _L, _P, _c.c_int32, _P, _P, _P, _P, _c.c_double, _I, _F, _P, _P, _P, _P,
                                                _F, _F, _F] + [_P] * 9),
     "ugrid_train_sample_dvgo_tensorf": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _L, _c.c_int32, _P, _P, _F, _F, _F, _P, _P, _P, _P, _F, _F, _F] + [_P] * 9),
+    "ugrid_frame_pack": (_I, [_P, _P, _P, _L, _L, _P, _P]),
+    "ugrid_frame_assemble": (_I, [_P, _P, _P, _P, _c.c_int32, _c.c_int32, _c.c_int32, _L, _c.c_int32, _c.c_int32, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -6,8 +6,8 @@ cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include"
 O=${UG_OBJ:-../../build/obj}      # UG_OBJ: separate object directory (parallel A/B builds)
 mkdir -p $O
-rm -f $O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o   # a failed compile must not link a stale object
-OBJS="$O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o"
+rm -f $O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o $O/ugrid_frame.o   # a failed compile must not link a stale object
+OBJS="$O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o $O/ugrid_frame.o"
 pids=()
 hipcc $FLAGS -c ugrid_ops.hip -o $O/ugrid_ops.o "$@" &
 pids+=($!)
@@ -28,6 +28,8 @@ pids+=($!)
 hipcc $FLAGS -c ugrid_metrics.hip -o $O/ugrid_metrics.o "$@" &      # (fp64 stencil: -ffp-contract=off is part of its arithmetic contract)
 pids+=($!)
 hipcc $FLAGS -c ugrid_tensorf.hip -o $O/ugrid_tensorf.o "$@" &
+pids+=($!)
+hipcc $FLAGS -c ugrid_frame.hip -o $O/ugrid_frame.o "$@" &
 pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done   # a bare `wait` returns 0 even when a job failed
 hipcc --offload-arch=gfx950 -shared -fPIC -o ${UG_OUT:-../libugrid_hip.so} $OBJS

@@ -83,6 +83,265 @@ def render_sharded(renderer_forward, rays_o, rays_d, viewdirs, group=None, inter
             "alphainv_last": full[:, 4].contiguous()}
 
 
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The frame pipeline: a view list over the process group, for every renderer of the package
+# ---------------------------------------------------------------------------------------------------------------------------
+_PLANS = {}
+DEALS = ("bands", "rows", "tiles")
+
+
+class FramePlan:
+    """Who renders which pixel of an H x W frame split over `world` ranks, and where a pixel's result lies in the all-gathered
+    buffer [world*per,5] -- pure host arithmetic, one object per key (FramePlan(...) returns the cached one).
+
+    Ray order: the 8 x 8 pixel-block order of fourier_render.pixel_tile_order when H and W are multiples of 8 (`tile8`), else image
+    order (q = y*W + x).  The split of the R = H*W ray positions: deal = 'bands' -> contiguous 64-aligned ranges (shard_bounds);
+    'tiles' -> 64-ray tiles dealt singly; 'rows' -> in groups of W/8 tiles, whole block rows of the image; deal_group > 0 -> in
+    groups of that many tiles whatever `deal` says (tile_assignment; `deal_group` of the plan is 0 for bands).
+    `per` = rows of a rank's block of the gathered buffer (rank 0 holds the largest share), `px(rank)` = the flat pixel indices
+    y*W + x a rank renders, in its ray order.  `source_row` is the closed form that ugrid_frame_assemble evaluates per pixel;
+    `src_index` is the same table built the slow way, rank by rank, for the tests and the CPU path."""
+
+    def __new__(cls, H, W, world, deal="bands", deal_group=0, tile=8):
+        H, W, world, dg, tile = int(H), int(W), int(world), int(deal_group or 0), int(tile)
+        if deal not in DEALS:
+            raise ValueError("deal must be one of %s (got %r)" % (DEALS, deal))
+        if H < 1 or W < 1 or world < 1 or dg < 0:
+            raise ValueError("FramePlan: H, W, world >= 1 and deal_group >= 0 expected (got %d, %d, %d, %d)" % (H, W, world, dg))
+        if dg == 0 and deal != "bands":
+            dg = max(1, W // 8) if deal == "rows" else 1
+        key = (H, W, world, dg, tile)
+        plan = _PLANS.get(key)
+        if plan is None:
+            if len(_PLANS) > 64:
+                _PLANS.clear()
+            plan = _PLANS[key] = object.__new__(cls)
+            plan._build(H, W, world, dg, tile)
+        return plan
+
+    def _build(self, H, W, world, dg, tile):
+        from .fourier_render import _morton_ok, pixel_tile_order
+        self.H, self.W, self.R, self.world, self.deal_group = H, W, H * W, world, dg
+        # (the kernel's block order is the Z-order one: with UGRID_TILE_MORTON=0 a plan stays in image order)
+        self.tile8 = tile == 8 and H % 8 == 0 and W % 8 == 0 and _morton_ok(8)
+        self.order = pixel_tile_order(H, W, torch.device("cpu"), 8).clone() if self.tile8 else None
+        self.per = tile_assignment(self.R, world, 0, group=dg).numel() if dg else shard_bounds(self.R, world, 0)[1]
+        self._src = None
+        self._px = {}
+
+    def positions(self, rank):
+        """ray positions q of `rank`, ascending within a tile, in the order the rank renders and sends them"""
+        if self.deal_group:
+            return tile_assignment(self.R, self.world, rank, group=self.deal_group).to(torch.int64)
+        b, e = shard_bounds(self.R, self.world, rank)
+        return torch.arange(b, e, dtype=torch.int64)
+
+    def px(self, rank, device=None):
+        """flat pixel indices of `rank` (int64, on `device`; default: the host), cached"""
+        key = (int(rank), str(device))
+        t = self._px.get(key)
+        if t is None:
+            q = self.positions(rank)
+            t = (q if self.order is None else self.order[q]).contiguous()
+            if device is not None:
+                t = t.to(device)
+            self._px[key] = t
+        return t
+
+    def source_row(self, pixel):
+        """row of the gathered buffer that holds flat pixel index `pixel` (int or int64 tensor): ugrid_frame_assemble's formula"""
+        p = torch.as_tensor(pixel, dtype=torch.int64)
+        q = p
+        if self.tile8:
+            y, x = p // self.W, p % self.W
+            lane = ((y & 4) << 3) | ((x & 4) << 2) | ((y & 2) << 2) | ((x & 2) << 1) | ((y & 1) << 1) | (x & 1)
+            q = ((y >> 3) * (self.W >> 3) + (x >> 3)) * 64 + lane
+        dg, ws, per = self.deal_group, self.world, self.per
+        if dg == 0:
+            rank, off = q // per, q % per
+        else:
+            t = q // 64
+            g = t // dg
+            rank, off = g % ws, ((g // ws) * dg + t % dg) * 64 + q % 64
+        return rank * per + off
+
+    def src_index(self):
+        """the table of source_row over all pixels, int64 [R], built from every rank's own list (cached)"""
+        if self._src is None:
+            pix_of_row = torch.full((self.world * self.per,), -1, dtype=torch.int64)
+            for r in range(self.world):
+                pr = self.px(r)
+                pix_of_row[r * self.per: r * self.per + pr.numel()] = pr
+            rows = torch.nonzero(pix_of_row >= 0).reshape(-1)
+            src = torch.full((self.R,), -1, dtype=torch.int64)
+            src[pix_of_row[rows]] = rows
+            self._src = src
+        return self._src
+
+
+def _stream_of(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def frame_pack(rgb, depth, last, per):
+    """A rank's send tile [per,5]: rows 0..n = rgb(3), depth, alphainv_last of its n rays, rows n..per zero (n = 0, three empty tensors, is
+    legal: a zero tile).  Device tensors: ugrid_frame_pack, one launch; host tensors: the torch composition (tests of the
+    exchange logic)."""
+    n = int(depth.shape[0])
+    out = torch.empty(per, 5, dtype=torch.float32, device=depth.device)
+    if not depth.is_cuda:
+        out.zero_()
+        out[:n, 0:3], out[:n, 3], out[:n, 4] = rgb, depth, last
+        return out
+    from . import _lib
+    rgb, depth, last = rgb.contiguous(), depth.contiguous(), last.contiguous()
+    _lib.require_f32(("rgb", rgb), ("depth", depth), ("last", last))
+    with _lib.guard(depth.device):
+        _lib.check(_lib.load().ugrid_frame_pack(_lib.ptr(rgb) if n else None, _lib.ptr(depth) if n else None, _lib.ptr(last) if n else None,
+                                                n, per, _lib.ptr(out), _stream_of(depth.device)), "frame_pack")
+    return out
+
+
+def frame_assemble(plan, gathered=None, rgb=None, depth=None, last=None):
+    """The packed frame [H*W,5] in image order from the gathered buffer [world*per,5] of `plan`, or (gathered None) from the three
+    per-ray arrays of a whole frame in the plan's ray order.  Device tensors: ugrid_frame_assemble, one launch, no index table;
+    host tensors: index_select with plan.src_index()."""
+    src = gathered if gathered is not None else depth
+    if not src.is_cuda:
+        if gathered is None:      # (whole frame in ray order: the rows of a one-rank plan)
+            gathered = torch.cat([rgb.reshape(-1, 3), depth.reshape(-1, 1), last.reshape(-1, 1)], dim=1)
+            plan = FramePlan(plan.H, plan.W, 1, tile=8 if plan.tile8 else 0)
+        return torch.index_select(gathered, 0, plan.src_index())
+    from . import _lib
+    out = torch.empty(plan.R, 5, dtype=torch.float32, device=src.device)
+    with _lib.guard(src.device):
+        if gathered is not None:
+            assert gathered.is_contiguous() and gathered.dtype == torch.float32 and gathered.numel() == plan.world * plan.per * 5
+            err = _lib.load().ugrid_frame_assemble(_lib.ptr(gathered), None, None, None, plan.H, plan.W, plan.world, plan.per,
+                                                   plan.deal_group, int(plan.tile8), _lib.ptr(out), _stream_of(src.device))
+        else:
+            rgb, depth, last = rgb.contiguous(), depth.contiguous(), last.contiguous()
+            _lib.require_f32(("rgb", rgb), ("depth", depth), ("last", last))
+            assert depth.numel() == plan.R and last.numel() == plan.R and rgb.numel() == 3 * plan.R
+            err = _lib.load().ugrid_frame_assemble(None, _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(last), plan.H, plan.W, 1, plan.R, 0,
+                                                   int(plan.tile8), _lib.ptr(out), _stream_of(src.device))
+        _lib.check(err, "frame_assemble")
+    return out
+
+
+class FramePipeline:
+    """A view list rendered over a process group, for FourierGridRenderer (and its composed twin) and the BoundedRenderer family
+    (DirectVoxGORenderer, DirectContractedVoxGORenderer, DirectMPIGORenderer -- NDC rays for the last).
+
+    submit(H, W, K, c2w, **kw) issues one view on the CURRENT stream: rays of this rank's pixels only (FramePlan.px), one render
+    pass, ugrid_frame_pack, and an asynchronous all_gather_into_tensor into one of two gathered buffers.  Just before the collective
+    is issued the PREVIOUS view is completed -- a stream-level wait for its collective, then ugrid_frame_assemble -- so a view's
+    exchange runs beside the next view's render.  submit returns the frame it completed (a packed [H*W,5] device tensor in image
+    order: rgb(3), depth, alphainv_last) or None; flush() completes the last one.  Frames come back in submission order, each once.
+    kw: stepsize, inverse_y, flip_x, flip_y, and for the bounded family near / far / bg (what run_render passes on).
+
+    Order rules (every one is needed; bench.py's FrameBench keeps the same):
+      * a gathered buffer goes into a new collective only after the issuing stream has waited on the event recorded behind the
+        assembly that read it (with views on several streams that assembly ran on another stream);
+      * a send tile is referenced until its collective has been waited for, and handed to the waiting stream before it is dropped;
+      * every rank issues its collectives in view order, a rank without rays included (it sends a zero tile);
+      * frame sizes may change from view to view: a plan per size, the buffers regrown.
+    Without a process group, or with one rank, there is no exchange: submit returns the view's own frame, assembled from the three
+    per-ray arrays.  On host tensors (gloo tests with a stand-in renderer) torch composes what the two kernels do."""
+
+    def __init__(self, model, group=None, deal="bands", deal_group=0):
+        on = dist.is_available() and dist.is_initialized()
+        self.model, self.group = model, group
+        self.device = torch.device(model.device)
+        self.world = dist.get_world_size(group) if on else 1
+        self.rank = dist.get_rank(group) if on else 0
+        self.deal, self.deal_group = deal or "bands", int(deal_group or 0)
+        self.ndc = bool(getattr(model, "ndc", False))
+        self._gathered = [None, None]
+        self._assembled_ev = [None, None]
+        self._inflight = None
+        self._n = 0
+
+    def _render(self, block_order, o, d, v, kw):
+        m = self.model
+        if hasattr(m, "fused_supported"):          # BoundedRenderer family: render_rays, as render_view_of calls it
+            rk = {k: kw[k] for k in ("near", "far", "stepsize", "bg") if k in kw}
+            if m.fused_supported():                # (the composed forward takes no ray_order)
+                ray_order = "coherent" if block_order else m.ray_order
+                if ray_order is not None:
+                    rk["ray_order"] = ray_order
+            return m.render_rays(o, d, v, render_depth=True, **rk)
+        return m.forward(o, d, v, stepsize=kw["stepsize"], ray_order="coherent" if block_order else "auto", render_depth=True)
+
+    def _rays(self, H, W, K, c2w, px, kw):
+        from .fourier_render import get_rays_of_pixel_index
+        return get_rays_of_pixel_index(H, W, K, c2w, px, inverse_y=bool(kw.get("inverse_y", False)), flip_x=bool(kw.get("flip_x", False)),
+                                       flip_y=bool(kw.get("flip_y", False)), ndc=self.ndc)
+
+    def render_local(self, H, W, K, c2w, **kw):
+        """one whole view on this device, no exchange: the packed frame [H*W,5]"""
+        from .fourier_render import get_rays_of_a_view, pixel_tile_order
+        plan = FramePlan(H, W, 1)
+        dev = self.device
+        c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
+        if plan.tile8:
+            o, d, v = self._rays(H, W, K, c2w, pixel_tile_order(H, W, dev, 8), kw)
+        else:
+            o, d, v = get_rays_of_a_view(H, W, K, c2w, inverse_y=bool(kw.get("inverse_y", False)), flip_x=bool(kw.get("flip_x", False)),
+                                         flip_y=bool(kw.get("flip_y", False)), ndc=self.ndc)
+            o, d, v = o.reshape(-1, 3).contiguous(), d.reshape(-1, 3).contiguous(), v.reshape(-1, 3).contiguous()
+        out = self._render(plan.tile8, o, d, v, kw)
+        return frame_assemble(plan, rgb=out["rgb_marched"], depth=out["depth"], last=out["alphainv_last"])
+
+    def submit(self, H, W, K, c2w, **kw):
+        if self.world == 1:
+            return self.render_local(H, W, K, c2w, **kw)
+        dev = self.device
+        cuda = dev.type == "cuda"
+        plan = FramePlan(H, W, self.world, self.deal, self.deal_group)
+        c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
+        px = plan.px(self.rank, dev)
+        if px.numel() > 0:
+            o, d, v = self._rays(H, W, K, c2w, px, kw)
+            out = self._render(plan.tile8, o, d, v, kw)
+            rgb, depth, last = out["rgb_marched"], out["depth"], out["alphainv_last"]
+        else:                                       # an empty share: a zero tile, and the rank still takes part in the collective
+            rgb, depth, last = torch.empty(0, 3, device=dev), torch.empty(0, device=dev), torch.empty(0, device=dev)
+        tile = frame_pack(rgb, depth, last, plan.per)
+        done = self._complete()                     # the previous view: wait for its exchange, assemble it beside this view's
+        k = self._n & 1
+        if cuda and self._assembled_ev[k] is not None:      # (the assembly that last read gathered[k] may have run on another stream)
+            torch.cuda.current_stream(dev).wait_event(self._assembled_ev[k])
+        need = self.world * plan.per * 5
+        buf = self._gathered[k]
+        if buf is None or buf.numel() < need:
+            if cuda and buf is not None:
+                buf.record_stream(torch.cuda.current_stream(dev))
+            buf = self._gathered[k] = torch.empty(need, dtype=torch.float32, device=dev)
+        full = buf[:need].view(self.world * plan.per, 5)
+        work = dist.all_gather_into_tensor(full, tile, group=self.group, async_op=True)
+        self._inflight = {"work": work, "tile": tile, "full": full, "plan": plan, "k": k}
+        self._n += 1
+        return done
+
+    def _complete(self):
+        fl, self._inflight = self._inflight, None
+        if fl is None:
+            return None
+        fl["work"].wait()                           # stream-level for a device collective
+        frame = frame_assemble(fl["plan"], gathered=fl["full"])
+        if self.device.type == "cuda":
+            st = torch.cuda.current_stream(self.device)
+            self._assembled_ev[fl["k"]] = st.record_event()
+            fl["tile"].record_stream(st)            # (allocated on the stream that sent it, released behind this stream's wait)
+        return frame
+
+    def flush(self):
+        """complete the last submitted view: its frame, or None when nothing is in flight"""
+        return self._complete()
+
+
 INVISIBLE_SCALE = 2.0 ** -60   # weight factor of a block that fails the visibility test (see composite_blocks)
 
 
