@@ -718,7 +718,9 @@ int ugrid_voxgo_step_backward_density(const ugrid_voxgo_step *s, ugrid_stream_t 
  * (fourier_freq_num, k0 channels, viewbase_pe) triple, else 0 (they return hipErrorNotSupported for it). */
 int ugrid_shade_supported(int32_t freq_num, int32_t k0_channels, int32_t viewbase_pe);
 
-/* Tuning knobs (speed only, never results): "march_waves" 4..6 (waves per SIMD of the march kernel); "tv_xcd" 0|1|2|3
+/* Tuning knobs (speed only, never results): "march_waves" 4..8 (waves per SIMD the FourierGrid march kernel is compiled for: 4..6 leave
+ * the brick loads of the level sum to the compiler, 7 and 8 issue them as a hand-pipelined ring of three levels behind counted vmcnt
+ * waits -- 63 VGPRs, so both are resident at 8 waves; default 8, and 0 restores the default; bit-identical frames); "tv_xcd" 0|1|2|3
  * (dense TV / TV + Adam kernels: linear workgroup order | XCD-contiguous | + non-temporal streams | + slab order (i-planes of a
  * j-slab stay in L2) for the fused channel-last pass, default 3);
  * "shade_pc" 0|1|2 (shade kernel geometry: classic | 8-wave producer / consumer | 12-wave where it applies, default 2 --

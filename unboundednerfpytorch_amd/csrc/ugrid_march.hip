@@ -1124,6 +1124,8 @@ static inline ug_march_geom ug_march_geometry(void *ws_mem, int64_t n_rays, int3
   return g;
 }
 
+// W = 4..6 waves per SIMD: the level sum with the brick loads left to the compiler (ug_density_level).  (The body is not shared with
+// k_march_ring through a helper: passing the arguments on changes the register allocation of these kernels throughout.)
 template <int F, bool L2, int W>
 __global__ void __launch_bounds__(256, W)
 k_march(ug_march_args a, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
@@ -1131,7 +1133,30 @@ k_march(ug_march_args a, const float *__restrict__ rays_o, const float *__restri
         const float *__restrict__ bricks, float *__restrict__ alphainv_last, float *__restrict__ depth,
         ug_ws_view ws, int64_t nblocks) {
   ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
-    return ug_march_tile<F, L2>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile, ent, slot);
+    if constexpr (ug_march_ring<W>::value) {   // (A/B builds with the ring at 6 waves only: as k_march_ring below)
+      tile = ug_wave_uniform(tile);
+      ent = ws.ent + tile * ws.cap;
+      slot = ws.slot + tile * ws.cap;
+    }
+    return ug_march_tile<F, L2, false, W>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile, ent, slot);
+  });
+}
+
+// W = 7 | 8: the same march with the level sum as a hand-pipelined ring of brick loads (ug_density_ring); a kernel of its own name,
+// with its own register caps (72 / 64, no scratch: tests/test_march_ring_budget.py)
+template <int F, bool L2, int W>
+__global__ void __launch_bounds__(256, W)
+k_march_ring(ug_march_args a, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+             const float *__restrict__ t_table, const float *__restrict__ s_table,
+             const float *__restrict__ bricks, float *__restrict__ alphainv_last, float *__restrict__ depth,
+             ug_ws_view ws, int64_t nblocks) {
+  static_assert(W == 7 || W == 8, "the ring is built for 7 and 8 waves per SIMD");
+  ug_march_block(ws, nblocks, [&](int64_t tile, float4 *ent, uint8_t *slot) {
+    // a wave owns a tile: say so, and the tile's list pointers (4 VGPRs) live in scalar registers
+    tile = ug_wave_uniform(tile);
+    ent = ws.ent + tile * ws.cap;
+    slot = ws.slot + tile * ws.cap;
+    return ug_march_tile<F, L2, false, W>(a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, tile, ent, slot);
   });
 }
 
@@ -1296,21 +1321,37 @@ extern "C" int ugrid_pack_bricks(const float *grid, int P, int C, int X, int Y, 
   return 0;
 }
 
-static int g_march_waves = 6;
-extern "C" int ug_set_march_waves(int w) { if (w < 4 || w > 6) return 1; g_march_waves = w; return 0; }
-  // min waves/SIMD the march kernel is compiled for (register cap 512/W)
+// min waves/SIMD the march kernel is compiled for (register cap 512/W): 4..6 = the level sum as plain C++ loads (ug_density_level),
+// 7 | 8 = ug_density_ring, three levels in flight behind hand-placed vmcnt waits; 0 = back to the default
+#define UG_MARCH_WAVES_DEFAULT 8
+static int g_march_waves = UG_MARCH_WAVES_DEFAULT;
+extern "C" int ug_set_march_waves(int w) {
+  if (w == 0) w = UG_MARCH_WAVES_DEFAULT;
+  if (w < 4 || w > 8) return 1;
+  g_march_waves = w;
+  return 0;
+}
 
 template <int F, int W>
 static int ug_march_launch_w(const ugrid_render_params *p, const ug_march_args &a, const float *rays_o,
                              const float *rays_d, const float *t_table, const float *s_table,
                              const float *bricks, float *alphainv_last, float *depth, const ug_march_geom &g,
                              hipStream_t st) {
-  if (p->norm_l2)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, true, W>), g.grid, dim3(256), 0, st, a, rays_o,
-                       rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, false, W>), g.grid, dim3(256), 0, st, a, rays_o,
-                       rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
+  if constexpr (W >= 7) {
+    if (p->norm_l2)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_ring<F, true, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                         rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march_ring<F, false, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                         rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
+  } else {
+    if (p->norm_l2)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, true, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                         rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_march<F, false, W>), g.grid, dim3(256), 0, st, a, rays_o,
+                         rays_d, t_table, s_table, bricks, alphainv_last, depth, g.ws, g.nblocks);
+  }
   UG_LAUNCH_CHECK();
   return 0;
 }
@@ -1323,6 +1364,8 @@ static int ug_march_launch(const ugrid_render_params *p, const ug_march_args &a,
   switch (g_march_waves) {
     case 4: return ug_march_launch_w<F, 4>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
     case 6: return ug_march_launch_w<F, 6>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
+    case 7: return ug_march_launch_w<F, 7>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
+    case 8: return ug_march_launch_w<F, 8>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
     default: return ug_march_launch_w<F, 5>(p, a, rays_o, rays_d, t_table, s_table, bricks, alphainv_last, depth, g, st);
   }
 }

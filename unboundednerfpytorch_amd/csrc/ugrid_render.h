@@ -175,6 +175,32 @@ struct ug_march_args {
   float shift, interval, thres;
 };
 
+// ---- explicit loads ------------------------------------------------------------------------------------------
+// hipcc sinks plain C++ loads down to their first use (one load in flight, s_waitcnt vmcnt(0) after each) or hoists
+// all of them (spills), whatever sched_barrier says, so the k0 gather issues its loads as volatile asm (program order
+// is kept among volatile asms) and waits with explicit s_waitcnt whose "+v" operands make every use of the loaded
+// registers depend on the wait.  The compiler's own vmcnt bookkeeping stays safe: memory operations return in order,
+// so loads it does not know about can only make its waits conservative.
+typedef float ug_f4 __attribute__((ext_vector_type(4)));
+template <int IMM>
+__device__ __forceinline__ ug_f4 ug_gload4(unsigned voff, const float *sbase) {
+  ug_f4 r;
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
+  return r;
+}
+// 64-bit address form (single-level k0 grids, F = 0: a 320^3 x 12-channel level is 12.5 GB, beyond the 32-bit offset of
+// the saddr + voffset form; with P = 1 the two extra address registers per item cost nothing)
+template <int IMM>
+__device__ __forceinline__ ug_f4 ug_gload4v(const char *vaddr) {
+  ug_f4 r;
+  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(vaddr), "n"(IMM) : "memory");
+  return r;
+}
+template <int N>
+__device__ __forceinline__ void ug_vmwait6(ug_f4 (&v)[6]) {
+  asm volatile("s_waitcnt vmcnt(%6)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]) : "n"(N));
+}
+
 // one density level: in-range cell set-up + one 32-byte brick + trilinear in grid_sample's order.
 // `lvl` is the (wave-uniform) base of this level's bricks; the per-lane offset stays 32-bit.
 __device__ __forceinline__ float ug_density_level(const char *__restrict__ lvl, float cx, float cy, float cz,
@@ -193,6 +219,141 @@ __device__ __forceinline__ float ug_density_level(const char *__restrict__ lvl, 
   const float p10 = fmaf(v1.y, tz, v1.x), p11 = fmaf(v1.w, tz, v1.z);   // x^1
   return fmaf(fmaf(p11, ty, p10), tx, fmaf(p01, ty, p00));
 }
+
+// ---- pipelined density (k_march_ring: 7 and 8 waves per SIMD) -------------------------------------------------------
+// The sum over the P = 2F+1 levels of ug_density_level, same arithmetic and same order of the additions (level 0, then
+// sin_k, cos_k for k = 0..F-1), as ONE software pipeline with NFL levels (2 dwordx4 each) in flight.  Under the 64-register
+// cap of 8 waves hipcc issues the plain C++ loads of ug_density_level two at a time, each pair followed by vmcnt(0) --
+// P exposed latencies per sample; here, right after level i's polynomial, level i+NFL is set up (coordinates, cell offset,
+// fractions) in the registers that polynomial freed, while the NFL-1 levels behind it are in flight, and issued.
+//
+// vmcnt: the waits are "at most N operations NEWER than the level I need are still out", N = 2 x levels issued after it.
+// Older operations -- the two survivor stores of the previous sample, which gfx950 counts in vmcnt too -- need not be
+// counted or drained: loads return in order among themselves, so any state with <= N outstanding that still held one of my
+// level's loads would also hold the 2 x (levels after it) newer loads, i.e. more than N of them.  An older store can only
+// keep the count up, and the wait conservative.  The ring is straight-line code between sched_barriers with no other
+// memory operation inside (no flat access, no scratch: the kernels are built only where ScratchSize is 0); the last
+// level waits vmcnt(0), so nothing of the ring is out when the compiler's own loads and stores follow.  Lanes that are
+// `done` are exec-masked for the whole ring -- loads and waits alike are per-wave instructions, the counts do not change.
+struct ug_ring_setup { unsigned off; float tx, ty, tz; };
+
+__device__ __forceinline__ ug_ring_setup ug_ring_cell(float cx, float cy, float cz, int X, int Y, int Z) {
+  const ug_axis_fast ax = ug_axis_inrange(cx, X), ay = ug_axis_inrange(cy, Y), az = ug_axis_inrange(cz, Z);
+  const unsigned row = (unsigned)fmaf(ax.cellf, (float)(Y - 1), ay.cellf);      // ug_density_level's offset, to the letter
+  ug_ring_setup r;
+  r.off = __umul24(row, (unsigned)(Z - 1) << 5) + ((unsigned)az.cell << 5);
+  r.tx = ax.whi; r.ty = ay.whi; r.tz = az.whi;
+  return r;
+}
+
+// ug_gload4 without the "memory" clobber: the bricks are read-only for the whole kernel, and a clobber inside the sample loop
+// makes hipcc fetch the wave-uniform t_table[j] / s_table[j] with vector loads and a vmcnt(0) each instead of s_load
+template <int IMM>
+__device__ __forceinline__ ug_f4 ug_gload4_ro(unsigned voff, const float *sbase) {
+  ug_f4 r;
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(IMM));
+  return r;
+}
+
+__device__ __forceinline__ void ug_vmwait2(ug_f4 (&v)[2], int n_after) {   // n_after: compile-time after unrolling
+  if (n_after == 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]));
+  else if (n_after == 1) asm volatile("s_waitcnt vmcnt(2)" : "+v"(v[0]), "+v"(v[1]));
+  else if (n_after == 2) asm volatile("s_waitcnt vmcnt(4)" : "+v"(v[0]), "+v"(v[1]));
+  else if (n_after == 3) asm volatile("s_waitcnt vmcnt(6)" : "+v"(v[0]), "+v"(v[1]));
+  else asm volatile("s_waitcnt vmcnt(8)" : "+v"(v[0]), "+v"(v[1]));
+}
+
+// a 64-bit value that every lane of the wave holds alike, moved to scalar registers (call with the whole wave active)
+__device__ __forceinline__ int64_t ug_wave_uniform(int64_t x) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// the lane id formed from a zero the compiler cannot see through, so that it is not merged with an earlier ug_lane() whose
+// register would then stay live in between
+__device__ __forceinline__ int ug_lane_again() {
+  int zero;
+  asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
+}
+
+// table[j] for a wave-uniform j, as a load from the constant address space: hipcc treats every volatile asm as a possible
+// store, so beside the ring it would fetch the never-written t_table / s_table entries with vector loads and a vmcnt(0) each
+__device__ __forceinline__ float ug_const_ld(const float *__restrict__ table, int j) {
+  return ((const __attribute__((address_space(4))) float *)table)[j];
+}
+
+template <int F, int NFL>
+__device__ __forceinline__ float ug_density_ring(const char *__restrict__ bkb, size_t lvl_bytes, float ux, float uy, float uz,
+                                                 int X, int Y, int Z) {
+  constexpr int P = 2 * F + 1;
+  static_assert(NFL >= 1 && NFL <= 5, "ug_vmwait2 counts up to 4 levels after the one waited for");
+  ug_ring_setup c[NFL];
+  ug_f4 v[NFL][2];
+  float qx = 0.f, qy = 0.f, qz = 0.f;          // cos coordinates of the current frequency, kept for the level after sin
+#define UG_RING_SETUP(l_)                                                                                              \
+  {                                                                                                                    \
+    if ((l_) == 0) c[0] = ug_ring_cell(ux, uy, uz, X, Y, Z);                                                           \
+    else if (((l_) & 1) == 0) c[(l_) % NFL] = ug_ring_cell(qx, qy, qz, X, Y, Z);                                       \
+    else {                                                                                                             \
+      float sx, sy, sz;                                                                                                \
+      if ((l_) == 1) {   /* |u| <= 1 < pi/2: no range reduction needed, bit-identical (ug_sincos_small) */            \
+        ug_sincos_small(ux, &sx, &qx); ug_sincos_small(uy, &sy, &qy); ug_sincos_small(uz, &sz, &qz);                   \
+      } else {                                                                                                         \
+        const float f = (float)(1 << ((l_) / 2));                                                                      \
+        ug_sincos(f * ux, &sx, &qx); ug_sincos(f * uy, &sy, &qy); ug_sincos(f * uz, &sz, &qz);                         \
+      }                                                                                                                \
+      c[(l_) % NFL] = ug_ring_cell(sx, sy, sz, X, Y, Z);                                                               \
+    }                                                                                                                  \
+  }
+#define UG_RING_ISSUE(l_)                                                                                              \
+  {                                                                                                                    \
+    const float *lb = (const float *)(bkb + (size_t)(l_) * lvl_bytes);                                                 \
+    v[(l_) % NFL][0] = ug_gload4_ro<0>(c[(l_) % NFL].off, lb);                                                         \
+    v[(l_) % NFL][1] = ug_gload4_ro<16>(c[(l_) % NFL].off, lb);                                                        \
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int l = 0; l < NFL && l < P; ++l) {
+    UG_RING_SETUP(l)
+    __builtin_amdgcn_sched_barrier(0);
+    UG_RING_ISSUE(l)
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float dens = 0.f;
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    ug_vmwait2(v[i % NFL], (P - 1 - i) < (NFL - 1) ? (P - 1 - i) : (NFL - 1));   // levels issued after level i
+    const ug_f4 v0 = v[i % NFL][0], v1 = v[i % NFL][1];
+    const float tz = c[i % NFL].tz, ty = c[i % NFL].ty, tx = c[i % NFL].tx;
+    const float p00 = fmaf(v0.y, tz, v0.x), p01 = fmaf(v0.w, tz, v0.z);
+    const float p10 = fmaf(v1.y, tz, v1.x), p11 = fmaf(v1.w, tz, v1.z);
+    const float d = fmaf(fmaf(p11, ty, p10), tx, fmaf(p01, ty, p00));
+    dens = (i == 0) ? d : dens + d;
+    // keep the level's math here: without the pin the scheduler hoists every later load above it (spills)
+    asm volatile("" :: "v"(dens));
+    __builtin_amdgcn_sched_barrier(0);
+    if (i + NFL < P) {   // level i's registers are free: set up level i + NFL in them while NFL - 1 levels are in flight, and issue it
+      UG_RING_SETUP(i + NFL)
+      __builtin_amdgcn_sched_barrier(0);
+      UG_RING_ISSUE(i + NFL)
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#undef UG_RING_SETUP
+#undef UG_RING_ISSUE
+  return dens;
+}
+
+// levels in flight of ug_density_ring: 11 registers a level (8 of data, 3 fractions; the offset dies at the issue) beside about 30 of
+// ray state and set-up temporaries.  3 levels fit the 64-register cap of 8 waves (63 allocated, every F); 4 levels need 74-75 and
+// spill under the 72 of 7 waves, so the 7-wave instantiation carries the ring of 3 as well (table: DESIGN.md 4.1)
+// (-DUG_MARCH_RING6=n, an A/B build only: the ring of n levels under the 80-register cap of 6 waves as well -- tools/experiments/ARMS.md)
+#ifndef UG_MARCH_RING6
+#define UG_MARCH_RING6 0
+#endif
+template <int W> struct ug_march_nfl { static constexpr int value = W >= 7 ? 3 : UG_MARCH_RING6; };
+template <int W> struct ug_march_ring { static constexpr bool value = W >= 7 || (W == 6 && UG_MARCH_RING6 > 0); };
 
 // ----------------------------------------------------------------------------------------------
 // leaves shared by the three tile functions below (and, for the mask cache, by the training samplers of ugrid_march.hip):
@@ -270,7 +431,8 @@ struct ug_dc_args : ug_mask_args {
 
 // March one 64-ray tile (lane = ray): writes alphainv_last / depth for the tile's rays, appends the
 // survivors to ent/slot (this wave's private list) and returns their count (wave-uniform).
-template <int F, bool L2, bool DC = false>
+// W = the waves per SIMD the calling kernel is bounded for: at W >= 7 the level sum is ug_density_ring (same values)
+template <int F, bool L2, bool DC = false, int W = 6>
 __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float *__restrict__ rays_o,
                                              const float *__restrict__ rays_d, const float *__restrict__ t_table,
                                              const float *__restrict__ s_table, const float *__restrict__ bricks,
@@ -305,7 +467,8 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
     float w = 0.f;
     float px = 0.f, py = 0.f, pz = 0.f;
     if (!done) {
-      const float t = t_table[j];
+      float t;
+      if constexpr (ug_march_ring<W>::value) t = ug_const_ld(t_table, j); else t = t_table[j];
       px = ox + dx * t; py = oy + dy * t; pz = oz + dz * t;
       // contraction p/|p| * (B - A/|p|) outside the unit cube / ball (FourierGrid_model.py:534-548)
       const float nrm = L2 ? ug_norm3_torch(px, py, pz) : fmaxf(fabsf(px), fmaxf(fabsf(py), fabsf(pz)));
@@ -335,7 +498,11 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
         if (keep) keep = ug_mask_lookup(dc, px, py, pz);
       }
       if (keep) {
-        float dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
+        float dens;
+        if constexpr (ug_march_ring<W>::value) {
+          dens = ug_density_ring<F, ug_march_nfl<W>::value>(bkb, lvl_bytes, ux, uy, uz, a.X, a.Y, a.Z);
+        } else {
+        dens = ug_density_level(bkb, ux, uy, uz, a.X, a.Y, a.Z);
 #pragma unroll
         for (int k = 0; k < F; ++k) {
           const float f = (float)(1 << k);
@@ -352,6 +519,7 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
           dens += ug_density_level(bkb + (size_t)(2 * k + 1) * lvl_bytes, sx, sy, sz, a.X, a.Y, a.Z);
           dens += ug_density_level(bkb + (size_t)(2 * k + 2) * lvl_bytes, cx_, cy_, cz_, a.X, a.Y, a.Z);
         }
+        }
         dens = ug_div_r(dens, (float)P, 1.0f / (float)P);   // mean over levels: Markstein division, 3 VALU instead of 10
         const float xs = dens + a.shift;
         const float alpha = ug_alpha(xs, a.interval);
@@ -363,7 +531,7 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
           T = (float)((double)T * (1. - (double)alpha));
           if (w > a.thres) {
             surv = true;
-            dsum += w * s_table[j];
+            if constexpr (ug_march_ring<W>::value) dsum += w * ug_const_ld(s_table, j); else dsum += w * s_table[j];
             if constexpr (DC) { if (inner) wmid += w; }
           }
           if ((double)T < 1e-3) done = true;
@@ -371,6 +539,16 @@ __device__ __forceinline__ int ug_march_tile(const ug_march_args &a, const float
       }
     }
     ug_append_survivors(surv, px, py, pz, w, lane, ent, slot, nsurv);
+  }
+  if constexpr (ug_march_ring<W>::value) {
+    // the ray index formed again from a lane id the compiler cannot merge with the first one: otherwise `ray` (2 VGPRs) stays
+    // live through the whole sample loop for these two stores
+    const int64_t ray2 = tile * UG_WAVE + ug_lane_again();
+    if (ray2 < a.n_rays) {
+      alphainv_last[ray2] = T;
+      depth[ray2] = dsum;
+    }
+    return nsurv;
   }
   if (valid) {
     alphainv_last[ray] = T;
@@ -659,32 +837,6 @@ __device__ __forceinline__ void ug_k0_gather(const float *__restrict__ k0b, int 
   }
 #pragma unroll
   for (int ch = 0; ch < CH; ++ch) feat[ch] = ug_div_r(feat[ch], (float)P, 1.0f / (float)P);
-}
-
-// ---- explicit loads ------------------------------------------------------------------------------------------
-// hipcc sinks plain C++ loads down to their first use (one load in flight, s_waitcnt vmcnt(0) after each) or hoists
-// all of them (spills), whatever sched_barrier says, so the k0 gather issues its loads as volatile asm (program order
-// is kept among volatile asms) and waits with explicit s_waitcnt whose "+v" operands make every use of the loaded
-// registers depend on the wait.  The compiler's own vmcnt bookkeeping stays safe: memory operations return in order,
-// so loads it does not know about can only make its waits conservative.
-typedef float ug_f4 __attribute__((ext_vector_type(4)));
-template <int IMM>
-__device__ __forceinline__ ug_f4 ug_gload4(unsigned voff, const float *sbase) {
-  ug_f4 r;
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(r) : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
-  return r;
-}
-// 64-bit address form (single-level k0 grids, F = 0: a 320^3 x 12-channel level is 12.5 GB, beyond the 32-bit offset of
-// the saddr + voffset form; with P = 1 the two extra address registers per item cost nothing)
-template <int IMM>
-__device__ __forceinline__ ug_f4 ug_gload4v(const char *vaddr) {
-  ug_f4 r;
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(vaddr), "n"(IMM) : "memory");
-  return r;
-}
-template <int N>
-__device__ __forceinline__ void ug_vmwait6(ug_f4 (&v)[6]) {
-  asm volatile("s_waitcnt vmcnt(%6)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]) : "n"(N));
 }
 
 // ---- quad k0 gather (C == 12) ----------------------------------------------------------------------------------
