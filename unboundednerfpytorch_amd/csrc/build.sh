@@ -6,31 +6,35 @@ cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include"
 O=${UG_OBJ:-../../build/obj}      # UG_OBJ: separate object directory (parallel A/B builds)
 mkdir -p $O
-rm -f $O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o $O/ugrid_frame.o   # a failed compile must not link a stale object
-OBJS="$O/ugrid_ops.o $O/ugrid_update.o $O/ugrid_march.o $O/ugrid_shade.o $O/ugrid_train.o $O/ugrid_train_mlp.o $O/ugrid_step.o $O/ugrid_metrics.o $O/ugrid_tensorf.o $O/ugrid_frame.o"
-pids=()
-hipcc $FLAGS -c ugrid_ops.hip -o $O/ugrid_ops.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_update.hip -o $O/ugrid_update.o "$@" &
-pids+=($!)
 # packed fp32 VALU (v_pk_*_f32 from the SLP vectoriser) issues at half rate on gfx950 and needs extra moves to form
-# register pairs: the VALU-bound march kernel is 16 % faster without it, the shade kernel 1.3 %
-hipcc $FLAGS -fno-slp-vectorize ${UG_MARCH_FLAGS} -c ugrid_march.hip -o $O/ugrid_march.o "$@" &
-pids+=($!)
-hipcc $FLAGS -fno-slp-vectorize ${UG_SHADE_FLAGS} -c ugrid_shade.hip -o $O/ugrid_shade.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_train.hip -o $O/ugrid_train.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_train_mlp.hip -o $O/ugrid_train_mlp.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_step.hip -o $O/ugrid_step.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_metrics.hip -o $O/ugrid_metrics.o "$@" &      # (fp64 stencil: -ffp-contract=off is part of its arithmetic contract)
-pids+=($!)
-hipcc $FLAGS -c ugrid_tensorf.hip -o $O/ugrid_tensorf.o "$@" &
-pids+=($!)
-hipcc $FLAGS -c ugrid_frame.hip -o $O/ugrid_frame.o "$@" &
-pids+=($!)
+# register pairs: the VALU-bound march kernel is 16 % faster without it, the shade kernel 1.3 %; the grid query
+# and the sampling march were part of the march unit and keep its flag (their code was built and measured under it)
+NOSLP=-fno-slp-vectorize
+# the units of the library, one `name:extra flags` each -- the only list: objects, compiles and the link follow from it
+# (ugrid_metrics: an fp64 stencil, -ffp-contract=off is part of its arithmetic contract)
+UNITS=(
+  "ugrid_ops:"
+  "ugrid_update:"
+  "ugrid_march:$NOSLP ${UG_MARCH_FLAGS}"
+  "ugrid_query:$NOSLP"
+  "ugrid_sample:$NOSLP"
+  "ugrid_shade:$NOSLP ${UG_SHADE_FLAGS}"
+  "ugrid_train:"
+  "ugrid_train_mlp:"
+  "ugrid_step:"
+  "ugrid_metrics:"
+  "ugrid_tensorf:"
+  "ugrid_frame:"
+)
+OBJS=""
+pids=()
+for u in "${UNITS[@]}"; do
+  name=${u%%:*}
+  OBJS="$OBJS $O/$name.o"
+  rm -f $O/$name.o               # a failed compile must not link a stale object
+  hipcc $FLAGS ${u#*:} -c $name.hip -o $O/$name.o "$@" &
+  pids+=($!)
+done
 for p in "${pids[@]}"; do wait "$p"; done   # a bare `wait` returns 0 even when a job failed
 hipcc --offload-arch=gfx950 -shared -fPIC -o ${UG_OUT:-../libugrid_hip.so} $OBJS
 # the fp64 twins of the drop-in ops: a library of its own (nothing on the rendering / training path loads it)

@@ -1,5 +1,5 @@
 // Ray / box / mask-cache leaves of the sample_pts_on_rays family, shared by the drop-in kernels of ugrid_ops.hip and the
-// stage set-up kernels (ugrid_hit_coarse_geo there, ugrid_count_views_accumulate in ugrid_march.hip).  Every expression here is
+// stage set-up kernels (ugrid_hit_coarse_geo there, ugrid_count_views_accumulate in ugrid_query.hip).  Every expression here is
 // a bit-exactness contract with the reference kernels (render_utils_kernel.cu, pinned by tests/golden/native_ops.npz): a kernel
 // that needs one of them calls it, none restates it.  Compiled with -ffp-contract=off like everything else (csrc/build.sh).
 #pragma once

@@ -1,5 +1,6 @@
 // ugrid_render.h -- device code of the fused FourierGrid render path for gfx950 (MI355X), shared by
-// ugrid_march.hip and ugrid_shade.hip (both compiled with -fno-slp-vectorize: packed v_pk_*_f32 math issues at
+// ugrid_march.hip and ugrid_shade.hip; ugrid_query.hip and ugrid_sample.hip use its per-sample math and mask cache
+// (all compiled with -fno-slp-vectorize: packed v_pk_*_f32 math issues at
 // half rate on gfx950 and costs extra moves -- a 16 % loss for the VALU-bound march kernel, 1.3 % for shade).
 //
 // Replaces, for inference, the torch-op chain of the reference's FourierGridModel.forward
@@ -356,7 +357,7 @@ template <int W> struct ug_march_nfl { static constexpr int value = W >= 7 ? 3 :
 template <int W> struct ug_march_ring { static constexpr bool value = W >= 7 || (W == 6 && UG_MARCH_RING6 > 0); };
 
 // ----------------------------------------------------------------------------------------------
-// leaves shared by the three tile functions below (and, for the mask cache, by the training samplers of ugrid_march.hip):
+// leaves shared by the three tile functions below (and, for the mask cache, by the training samplers of ugrid_sample.hip):
 // every rule that is a bit-exactness contract with the reference is written once, here
 // ----------------------------------------------------------------------------------------------
 // ((p - lo) / (hi - lo)) * 2 - 1 per axis

@@ -1,5 +1,5 @@
 // The lookup leaves of a TensoRF (vector-matrix) grid, shared by csrc/ugrid_tensorf.hip (query, backward, TV, bake) and the fused
-// sampling march of csrc/ugrid_march.hip (k_train_march_tensorf): ONE definition of the factorised density.  Every translation unit
+// sampling march of csrc/ugrid_sample.hip (k_train_march_tensorf): ONE definition of the factorised density.  Every translation unit
 // of the library is built with -ffp-contract=off, so one source expression gives one result in every kernel that includes this.
 #pragma once
 #include "ugrid_common.h"
