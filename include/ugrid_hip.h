@@ -479,6 +479,27 @@ int ugrid_rays_of_a_view_ndc(int32_t H, int32_t W, const float *h_K9, const floa
                              int mode_center, const int64_t *pixel_index, int64_t n, float near, float *rays_o,
                              float *rays_d, float *viewdirs, ugrid_stream_t stream);
 
+/* One iteration's ray batch straight from a pose table (train_rays.RayBatcher): what run_train.py:203-245 gathers from the
+ * materialised tables of get_training_rays_flatten / FourierGrid_get_training_rays (60 B per pixel) is produced from the pixel
+ * index, so that only the images (12 B or 3 B per pixel) and one record per view stay resident.
+ * cams: DEVICE [n_views] records (96 B); kx, ky are read with ndc only: (float)(-1. / ((double)W / (2. * (double)fx))) and the same
+ * with H, formed on the host like ugrid_rays_of_a_view_ndc forms them.  view_start: DEVICE [n_views + 1] prefix of the views' pixel
+ * counts.  index: DEVICE [n] global pixel indices in [0, view_start[n_views]) -- NOT checked on the device.  images: DEVICE
+ * [total,3], image_kind 0 = float32, 1 = uint8 (colour = (float)((double)u / 255.0)).  Outputs [n,3] each: the image row, the ray
+ * of ugrid_rays_of_a_view (ndc = 0) or ugrid_rays_of_a_view_ndc (ndc != 0, with `near`) bit for bit, and -- indexs != NULL -- the
+ * view number as float in all three columns (the reference's indexs_tr).  One launch; n <= 0 returns 0 without one. */
+typedef struct ugrid_ray_cam {
+  float fx, fy, cx, cy;
+  int32_t W, H;
+  float c2w[12];
+  float kx, ky;
+  float reserved[4];
+} ugrid_ray_cam;
+int ugrid_ray_batch(const ugrid_ray_cam *cams, const int64_t *view_start, int32_t n_views, const int64_t *index, int64_t n,
+                    const void *images, int image_kind, int inverse_y, int flip_x, int flip_y, int mode_center, int ndc,
+                    float near, float *target, float *rays_o, float *rays_d, float *viewdirs, float *indexs,
+                    ugrid_stream_t stream);
+
 /* ------------------------------------------------------------------ fused training forward, stage 1 (new)
  * Replaces the head of FourierGridModel.forward in training mode (FourierGrid_model.py:554-598): sample_ray, the
  * density lookup on all R*S points, Raw2Alpha, the `alpha > fast_color_thres` mask and its boolean-index gathers.

@@ -458,19 +458,34 @@ __device__ __forceinline__ void ug_view_ray_dir(const ug_cam &c, const float *__
   }
 }
 
+// one ray of a view: o = c2w[:,3], d = the world direction of flat pixel p, v = d / |d|  (the per-ray body that
+// k_rays_of_a_view and k_ray_batch share)
+__device__ __forceinline__ void ug_view_ray(const ug_cam &c, const float *__restrict__ c2w, int64_t p, float (&o)[3], float (&d)[3],
+                                            float (&v)[3]) {
+  ug_view_ray_dir(c, c2w, p, d);
+  const float nrm = sqrtf(fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0])));
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    o[a] = c2w[4 * a + 3];
+    v[a] = d[a] / nrm;
+  }
+}
+
+__device__ __forceinline__ void ug_store3(float *__restrict__ dst, int64_t t, const float (&x)[3]) {
+  dst[3 * t] = x[0];
+  dst[3 * t + 1] = x[1];
+  dst[3 * t + 2] = x[2];
+}
+
 __global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
                                  float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
-  float r[3];
-  ug_view_ray_dir(c, c2w, pix ? pix[t] : t, r);
-  const float nrm = sqrtf(fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0])));
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    rays_o[3 * t + a] = c2w[4 * a + 3];
-    rays_d[3 * t + a] = r[a];
-    viewdirs[3 * t + a] = r[a] / nrm;
-  }
+  float o[3], d[3], v[3];
+  ug_view_ray(c, c2w, pix ? pix[t] : t, o, d, v);
+  ug_store3(rays_o, t, o);
+  ug_store3(rays_d, t, d);
+  ug_store3(viewdirs, t, v);
 }
 
 // get_rays_of_a_view(ndc=True) (dvgo.py:534-559): viewdirs from the WORLD direction, then ndc_rays(H, W, K[0][0], near, o, d)
@@ -478,25 +493,87 @@ __global__ void k_rays_of_a_view(ug_cam c, const float *__restrict__ c2w, const 
 // (Tensor.__rtruediv__); the Python constants -1 / (W / (2 focal)) etc. are formed in double on the host and rounded to fp32.
 struct ug_ndc { float near, kx, ky, two_near, mtwo_near; };
 
-__global__ void k_rays_of_a_view_ndc(ug_cam c, ug_ndc q, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
-                                     float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
+// the NDC ray of flat pixel p (the per-ray body that k_rays_of_a_view_ndc and k_ray_batch share)
+__device__ __forceinline__ void ug_view_ray_ndc(const ug_cam &c, const ug_ndc &q, const float *__restrict__ c2w, int64_t p,
+                                                float (&o)[3], float (&d)[3], float (&v)[3]) {
   float r[3];
-  ug_view_ray_dir(c, c2w, pix ? pix[t] : t, r);
+  ug_view_ray_dir(c, c2w, p, r);
   const float nrm = sqrtf(fmaf(r[2], r[2], fmaf(r[1], r[1], r[0] * r[0])));
 #pragma unroll
-  for (int a = 0; a < 3; ++a) viewdirs[3 * t + a] = r[a] / nrm;
+  for (int a = 0; a < 3; ++a) v[a] = r[a] / nrm;
   const float wx = c2w[3], wy = c2w[7], wz = c2w[11];
   const float tt = -(wz + q.near) / r[2];
   const float ox = wx + tt * r[0], oy = wy + tt * r[1], oz = wz + tt * r[2];
   const float rz = 1.0f / oz;
-  rays_o[3 * t] = q.kx * ox / oz;
-  rays_o[3 * t + 1] = q.ky * oy / oz;
-  rays_o[3 * t + 2] = 1.0f + rz * q.two_near;
-  rays_d[3 * t] = q.kx * (r[0] / r[2] - ox / oz);
-  rays_d[3 * t + 1] = q.ky * (r[1] / r[2] - oy / oz);
-  rays_d[3 * t + 2] = rz * q.mtwo_near;
+  o[0] = q.kx * ox / oz;
+  o[1] = q.ky * oy / oz;
+  o[2] = 1.0f + rz * q.two_near;
+  d[0] = q.kx * (r[0] / r[2] - ox / oz);
+  d[1] = q.ky * (r[1] / r[2] - oy / oz);
+  d[2] = rz * q.mtwo_near;
+}
+
+__global__ void k_rays_of_a_view_ndc(ug_cam c, ug_ndc q, const float *__restrict__ c2w, const int64_t *__restrict__ pix, int64_t n,
+                                     float *__restrict__ rays_o, float *__restrict__ rays_d, float *__restrict__ viewdirs) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  float o[3], d[3], v[3];
+  ug_view_ray_ndc(c, q, c2w, pix ? pix[t] : t, o, d, v);
+  ug_store3(rays_o, t, o);
+  ug_store3(rays_d, t, d);
+  ug_store3(viewdirs, t, v);
+}
+
+// One iteration's ray batch from the pose table (train_rays.RayBatcher): a lane per batch row.  The row's global pixel index
+// -> its view by binary search over the prefix of pixel counts (the LAST view whose start is <= the index, so that views
+// without pixels are stepped over) -> the view's record -> the shared per-ray leaf; the colour comes from the flattened image
+// store, float32 or 8-bit ((float)((double)u / 255.0): the value of the loaders' (img / 255.).astype(np.float32)).
+// indexs (nullable): the view number as float in all three columns, like the reference's indexs_tr.
+__global__ void k_ray_batch(const ugrid_ray_cam *__restrict__ cams, const int64_t *__restrict__ view_start, int n_views,
+                            const int64_t *__restrict__ index, int64_t n, const void *__restrict__ images, int image_kind,
+                            int inverse_y, int flip_x, int flip_y, int center, int ndc, float near, float two_near, float mtwo_near,
+                            float *__restrict__ target, float *__restrict__ rays_o, float *__restrict__ rays_d,
+                            float *__restrict__ viewdirs, float *__restrict__ indexs) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t g = index[t];
+  int lo = 0, hi = n_views;             // view_start[lo] <= g < view_start[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (view_start[mid] <= g) lo = mid; else hi = mid;
+  }
+  const ugrid_ray_cam *__restrict__ rec = cams + lo;
+  ug_cam c;
+  c.fx = rec->fx; c.fy = rec->fy; c.cx = rec->cx; c.cy = rec->cy;
+  c.W = rec->W; c.H = rec->H; c.inverse_y = inverse_y; c.flip_x = flip_x; c.flip_y = flip_y; c.center = center;
+  const int64_t p = g - view_start[lo];
+  float o[3], d[3], v[3];
+  if (ndc) {
+    ug_ndc q;
+    q.near = near; q.kx = rec->kx; q.ky = rec->ky; q.two_near = two_near; q.mtwo_near = mtwo_near;
+    ug_view_ray_ndc(c, q, rec->c2w, p, o, d, v);
+  } else {
+    ug_view_ray(c, rec->c2w, p, o, d, v);
+  }
+  float rgb[3];
+  if (image_kind == 1) {
+    const uint8_t *__restrict__ im = (const uint8_t *)images + 3 * g;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rgb[a] = (float)((double)im[a] / 255.0);
+  } else {
+    const float *__restrict__ im = (const float *)images + 3 * g;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rgb[a] = im[a];
+  }
+  ug_store3(target, t, rgb);
+  ug_store3(rays_o, t, o);
+  ug_store3(rays_d, t, d);
+  ug_store3(viewdirs, t, v);
+  if (indexs) {
+    const float f = (float)lo;
+    const float fi[3] = {f, f, f};
+    ug_store3(indexs, t, fi);
+  }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -708,6 +785,20 @@ extern "C" int ugrid_rays_of_a_view_ndc(int32_t H, int32_t W, const float *h_K9,
   q.mtwo_near = (float)(-2. * nr);
   hipLaunchKernelGGL(k_rays_of_a_view_ndc, dim3(ug_blocks(n, 256)), dim3(256), 0, ST(s), c, q, c2w, pixel_index, n, rays_o,
                      rays_d, viewdirs);
+  UG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ugrid_ray_batch(const ugrid_ray_cam *cams, const int64_t *view_start, int32_t n_views, const int64_t *index,
+                               int64_t n, const void *images, int image_kind, int inverse_y, int flip_x, int flip_y,
+                               int mode_center, int ndc, float near, float *target, float *rays_o, float *rays_d, float *viewdirs,
+                               float *indexs, ugrid_stream_t s) {
+  if (n <= 0) return 0;
+  if (n_views <= 0 || (image_kind != 0 && image_kind != 1)) return (int)hipErrorInvalidValue;
+  const double nr = (double)near;
+  hipLaunchKernelGGL(k_ray_batch, dim3(ug_blocks(n, 256)), dim3(256), 0, ST(s), cams, view_start, (int)n_views, index, n, images,
+                     image_kind, inverse_y, flip_x, flip_y, mode_center, ndc, near, (float)(2. * nr), (float)(-2. * nr), target,
+                     rays_o, rays_d, viewdirs, indexs);
   UG_LAUNCH_CHECK();
   return 0;
 }
