@@ -831,6 +831,41 @@ int ugrid_frame_pack(const float *rgb, const float *depth, const float *last, in
 int ugrid_frame_assemble(const float *gathered, const float *rgb, const float *depth, const float *last, int32_t H, int32_t W,
                          int32_t world, int64_t per, int32_t deal_group, int32_t tile8, float *out, ugrid_stream_t stream);
 
+/* ------------------------------------------------------------------ 8-bit video frames from packed frames (csrc/ugrid_video.hip)
+ * The bytes the reference's render program (FourierGrid/run_render.py) forms with numpy from render_viewpoints' float stacks.
+ * to8b(x) = (uint8) trunc(255.0f * min(max(x, 0), 1)) in fp32; NaN -> 0 (this library's rule: numpy's cast of NaN is undefined).
+ * Orientation of every output: np.rot90(np.flip(img, 0) if flipy else img, k, axes=(0,1)) of the H x W source for any integer
+ * k, so the output is H' x W' = W x H for odd k.  The source pixel is computed, no index table is read:
+ *   video_plan (host arithmetic only): plan[5] = H', W', s0, si, sj -- output pixel (i, j) is source pixel s0 + i*si + j*sj.
+ * `out` may have any alignment; only its H'*W'*C bytes are written.  32-bit index arithmetic: hipErrorInvalidValue, before
+ * anything touches the device, for H or W <= 0, H*W*stride or H*W*C (+ 32) beyond INT32_MAX, stride < 5, a null frame / out.
+ *
+ * frame_rgb8: frame = packed [H*W,5] rows `stride` floats apart (stride >= 5); out uint8 [H',W',3] = to8b(rgb).  Optional, in the
+ *   same pass: db [H*W,2] = the pixel's (depth, alphainv_last), bit for bit, in SOURCE pixel order; dmax_key = one device word,
+ *   ZEROED by the caller before the first call, that holds the running maximum of depth over every call handed it, as the
+ *   order-preserving key  u = bits(d); key = u & 0x80000000 ? ~u : u | 0x80000000  (integer atomic max: order-independent).
+ * depth8_max: db [H*W,2]; out uint8 [H',W',1] = to8b(1.0f - d / dmax), fp32, IEEE division; dmax == 0 -> 0 everywhere.
+ * depth8_map: out uint8 [H',W',3] = table[i] (table: device uint8 [256,3]) with v = d*(1 - b) + b (each operation rounded to fp32),
+ *   then in fp64 t = clip((v - dmin) / (dmax - dmin), 0, 1), x = 1 - t, i = (int)(x*256), 256 -> 255; NaN x -> (0,0,0).
+ * depthvis_select: db [n,2] (any number of frames).  A pixel takes part when b < thres; *cnt (host) = how many do; values[r]
+ *   (host, r < m <= 4) = the exact ranks[r]-th smallest (0-based, ranks ascending) v = d*(1 - b) + b of those, ordered as np.sort
+ *   orders floats (-0.0 and +0.0 are one value there: either may come back; NaN of positive sign last).  Radix select on the key
+ *   above, passes of 11 / 11 / 10 bits: LDS histograms, integer atomics only, the host reads the counters between passes -- the
+ *   call SYNCHRONISES `stream` (three times) and returns host values; the same input gives the same answer in every run.
+ *   ws: ugrid_depthvis_select_ws_bytes() device bytes.  hipErrorInvalidValue: n < 0 or > INT32_MAX, m < 0 or > 4, ranks negative or
+ *   not ascending (before any launch, nothing written); a rank >= the count (after the first pass: *cnt is written, values are not).
+ *   n == 0 launches nothing. */
+int ugrid_video_plan(int64_t H, int64_t W, int32_t flipy, int32_t k, int64_t *plan);
+int ugrid_frame_rgb8(const float *frame, int64_t stride, int64_t H, int64_t W, int32_t flipy, int32_t k, uint8_t *out, float *db,
+                     uint32_t *dmax_key, ugrid_stream_t stream);
+int ugrid_depth8_max(const float *db, int64_t H, int64_t W, int32_t flipy, int32_t k, float dmax, uint8_t *out,
+                     ugrid_stream_t stream);
+int ugrid_depth8_map(const float *db, int64_t H, int64_t W, int32_t flipy, int32_t k, double dmin, double dmax,
+                     const uint8_t *table, uint8_t *out, ugrid_stream_t stream);
+int64_t ugrid_depthvis_select_ws_bytes(void);
+int ugrid_depthvis_select(const float *db, int64_t n, float thres, int32_t m, const int64_t *ranks, int64_t *cnt, float *values,
+                          void *ws, ugrid_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

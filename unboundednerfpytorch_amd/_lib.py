@@ -198,6 +198,12 @@ _SIGNATURES = {
     "ugrid_train_sample_dvgo_tensorf": (_I, [_P] * 6 + [_I] * 6 + [_P, _P, _L, _c.c_int32, _P, _P, _F, _F, _F, _P, _P, _P, _P, _F, _F, _F] + [_P] * 9),
     "ugrid_frame_pack": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "ugrid_frame_assemble": (_I, [_P, _P, _P, _P, _c.c_int32, _c.c_int32, _c.c_int32, _L, _c.c_int32, _c.c_int32, _P, _P]),
+    "ugrid_video_plan": (_I, [_L, _L, _c.c_int32, _c.c_int32, _P]),
+    "ugrid_frame_rgb8": (_I, [_P, _L, _L, _L, _c.c_int32, _c.c_int32, _P, _P, _P, _P]),
+    "ugrid_depth8_max": (_I, [_P, _L, _L, _c.c_int32, _c.c_int32, _F, _P, _P]),
+    "ugrid_depth8_map": (_I, [_P, _L, _L, _c.c_int32, _c.c_int32, _c.c_double, _c.c_double, _P, _P, _P]),
+    "ugrid_depthvis_select_ws_bytes": (_L, []),
+    "ugrid_depthvis_select": (_I, [_P, _L, _F, _c.c_int32, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

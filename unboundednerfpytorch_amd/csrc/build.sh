@@ -11,7 +11,7 @@ mkdir -p $O
 # and the sampling march were part of the march unit and keep its flag (their code was built and measured under it)
 NOSLP=-fno-slp-vectorize
 # the units of the library, one `name:extra flags` each -- the only list: objects, compiles and the link follow from it
-# (ugrid_metrics: an fp64 stencil, -ffp-contract=off is part of its arithmetic contract)
+# (ugrid_metrics: an fp64 stencil, -ffp-contract=off is part of its arithmetic contract; ugrid_video: the same for its byte values)
 UNITS=(
   "ugrid_ops:"
   "ugrid_update:"
@@ -25,6 +25,7 @@ UNITS=(
   "ugrid_metrics:"
   "ugrid_tensorf:"
   "ugrid_frame:"
+  "ugrid_video:"
 )
 OBJS=""
 pids=()
